@@ -5,8 +5,25 @@ One step = integrating the ensemble from t=0 to tf=10 s with the CVODE-style BDF
 atol 1e-10) on MI355X. Inputs are synthetic, generated per rank for its own
 contiguous shard and resident in HBM before timing. Reactors are independent, so ranks share no
 data during integration; at N > 1 the final states and counters are all-gathered over RCCL once per
-step, inside the timed region. `value_incl_h2d_d2h` repeats one step with host-resident inputs and
-the results copied back (the PCIe-inclusive rate of BASELINE.md's definition).
+step, inside the timed region.
+
+A plain run does only what the headline figure needs: set-up, the warm-up steps, the --steps timed
+steps, the optional --dump-outputs, and the result line (its roofline block is arithmetic on the
+timed steps' own kernel times and counters plus the committed profiles/*.json, no run of its own).
+Everything that takes runs of its own is behind --full, and its fields are null without it:
+  cpu_baseline, parity_vs_oracle  the C CPU oracle on a sample, and the GPU results checked against it
+                                  (--no-cpu leaves it out of a --full run)
+  roofline.rate_jacobian          the phase split of the diagnostic build, in a child process (--no-phase)
+  value_incl_h2d_d2h              one more step with host-resident inputs and the results copied back,
+                                  the PCIe-inclusive rate of BASELINE.md's definition (--no-pcie)
+  gather_ms                       at N > 1, the all-gather alone
+
+--dump-outputs DIR writes what the last timed step handed its caller, as float64 .npy files (rank 0;
+at N > 1 the gathered ensemble): U.npy [rows, n] the final states, stats.npy [rows, len(DUMP_STATS)]
+the solver counters in DUMP_STATS order (the shader-clock columns of br_stats differ from run to run
+and are left out). At most DUMP_BYTES in all: a larger ensemble is sampled, the same seeded rows
+every run, and rows.npy holds their reactor indices (all of them otherwise). The inputs are a
+function of the arguments alone (ensemble.make_inputs), so two builds can be compared row by row.
 
 Scaling (BASELINE.json: "ensemble of 1e5 reactors, sharded over 1/2/4/8 GPUs"):
   --scaling strong (default): the config's total N (1e5 for GRI) is split into contiguous slices
@@ -14,7 +31,8 @@ Scaling (BASELINE.json: "ensemble of 1e5 reactors, sharded over 1/2/4/8 GPUs"):
   --scaling weak:             every rank integrates N reactors (--n).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config gri|h2o2|surf|gas_surf]
-                  [--scaling strong|weak] [--n N] [--no-cpu] [--no-phase] [--dry-run]
+                  [--scaling strong|weak] [--n N] [--dump-outputs DIR] [--full [--no-cpu] [--no-phase]
+                  [--no-pcie]] [--dry-run]
 
 Launch: under torch.distributed.run (WORLD_SIZE set) every process is one rank. Without a launcher,
 --gpus N > 1 makes this process spawn N rank processes (RANK / LOCAL_RANK / WORLD_SIZE, rendezvous on
@@ -42,6 +60,12 @@ HBM_ACHIEVABLE_GBS = 6300.0   # achievable HBM read rate (MI355X_MICROARCH.md, H
 # reactors of the workload. scripts/parity_outliers.py derives tests/parity_bands.py's bounds from the
 # oracle's own spread on exactly these reactors.
 PARITY_SAMPLE = {"gri": (8000, 2000), "gas_surf": (3000, 1000), "h2o2": (50000, 2000), "surf": (50000, 2000)}
+# --dump-outputs: the deterministic br_stats columns (the cyc_* shader-clock columns are timings), the
+# byte budget of the whole dump and the seed of the row sample taken when the ensemble exceeds it
+DUMP_STATS = ("nsteps", "nfe", "nje", "nsetups", "nni", "ncfn", "netf", "status", "t_end", "t_ign", "ign_rate",
+              "ign_dt", "nfe_dq")
+DUMP_BYTES = 60 * 10**6
+DUMP_SEED = 20250711
 CONFIGS = {
     "gri": dict(gas="grimech.dat", surf=None, n=100000, tf=10.0,
                 name="C3 test/batch_ch4 GRI-Mech 3.0 CH4/O2/N2 ensemble (53 species, 325 reactions)"),
@@ -75,10 +99,14 @@ def main():
     ap.add_argument("--n", type=int, default=0, help="total reactors (strong) or reactors per GPU (weak); "
                                                      "default: the config's N")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-phase", action="store_true", help="skip the rate+Jacobian phase split (diag build)")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive extra step (counter runs: "
-                                                          "one integrator dispatch per timed step only)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: CPU oracle "
+                    "baseline + parity, phase split, PCIe-inclusive step, the gather alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's final states and solver "
+                    "counters to DIR/*.npy (float64, at most 60 MB: a fixed seeded row sample beyond that)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU oracle baseline and parity leg")
+    ap.add_argument("--no-phase", action="store_true", help="with --full: skip the rate+Jacobian phase split "
+                                                           "(diag build)")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the PCIe-inclusive extra step")
     ap.add_argument("--dry-run", action="store_true", help="launch + sharding over gloo, no GPU (CPU test)")
     ap.add_argument("--phase-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -159,6 +187,10 @@ def main():
     torch.cuda.synchronize()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dist if world > 1 else None, dev)
 
+    outputs = None
+    if args.dump_outputs and rank == 0:   # before the --full legs run further steps into dU / dst
+        outputs = dump_outputs(args.dump_outputs, *(gathered[0] if world > 1 else (dU, dst)), pkg.STAT_FIELDS)
+
     st = dst.cpu().numpy()
     stats = {k: st[:, i] for i, k in enumerate(pkg.STAT_FIELDS)}
     nbad = int(np.sum(stats["status"] != 0))
@@ -191,7 +223,7 @@ def main():
     dj, dram_src = newest("dram")
 
     gather_ms = None
-    if world > 1:   # the gather alone (it is also inside every timed step above)
+    if world > 1 and args.full:   # the gather alone (it is also inside every timed step above)
         torch.cuda.synchronize()
         g0 = time.perf_counter()
         shard.gather_ensemble(dU, dst, dist, total if args.scaling == "strong" else None)
@@ -202,14 +234,14 @@ def main():
     # the inputs in pinned host memory and the final states + counters copied back to it. Reported
     # beside `value` (which, per the bench contract, starts with the inputs resident in HBM).
     pcie_s = None
-    if not args.no_pcie:
+    if args.full and not args.no_pcie:
         pcie_s = pcie_step(torch, dist, world, dev, (T, Asv, U0, tf), (dT, dA, dU0, dtf), dU, dst, step, gathered, shard)
 
     cpu = parity = phases = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu, parity = cpu_baseline(mech, args.config, T, Asv, U0, tf, dU.cpu().numpy(), stats["status"],
                                    args.cpu_seconds, eng)
-    if rank == 0 and world == 1 and not args.no_phase:
+    if rank == 0 and world == 1 and args.full and not args.no_phase:
         phases = run_phase_split(args.config)
 
     if rank == 0:
@@ -282,10 +314,33 @@ def main():
             "gather_ms": gather_ms,
             "gather_in_timed_region": world > 1,
             "value_incl_h2d_d2h": (ok_all / pcie_s) if pcie_s else None,
+            "full": args.full,
+            "outputs": outputs,
         }
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, dU, dst, stat_fields):
+    """--dump-outputs: the final states and the deterministic solver counters of the last timed step as
+    float64 .npy files under out_dir, at most DUMP_BYTES in all. A larger ensemble is cut to a sorted
+    row sample drawn from DUMP_SEED (the same rows for the same shape); rows.npy names the rows kept."""
+    U = dU.cpu().numpy()
+    st = dst.cpu().numpy()
+    S = np.ascontiguousarray(st[:, [stat_fields.index(k) for k in DUMP_STATS]])
+    n_rows = U.shape[0]
+    row_bytes = 8 * (U.shape[1] + S.shape[1] + 1)
+    keep = min(n_rows, (DUMP_BYTES - 3 * 1024) // row_bytes)   # (3 .npy headers)
+    rows = np.arange(n_rows)
+    if keep < n_rows:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"U": U[rows], "stats": S[rows], "rows": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "rows": int(keep), "of": int(n_rows), "stats_columns": list(DUMP_STATS),
+            "arrays": {name: list(a.shape) for name, a in arrays.items()}}
 
 
 def spawn_ranks(n):

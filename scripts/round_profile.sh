@@ -16,10 +16,11 @@ if [ -z "$NO_PMC" ]; then
   bash scripts/pmc_all.sh $CFGS || exit $?
   for c in $CFGS; do cp gpurun_out/${TAG}_traffic_$c.json profiles/${TAG}_traffic_$c.json; cp gpurun_out/${TAG}_traffic_$c.json gpurun_out/profiles/; done
 fi
+LOGS=${LOGS:-bench_logs}; mkdir -p $LOGS   # the full bench lines: copy $LOGS/${TAG}_bench_*.json to profiles/ as well
 for c in $CFGS; do
-  timeout -k 10 400 python3 bench.py --config $c > gpurun_out/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -5 gpurun_out/bench_$c.log; exit 1; }
-  tail -1 gpurun_out/bench_$c.log > gpurun_out/profiles/${TAG}_bench_$c.json
-  python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], round(d['value']), round(r['kernel_ms'],1), 'frac', round(r['frac'],4), 'traffic/reactor', (r['traffic'] or 0)/d['config']['reactors_rank0'])" gpurun_out/profiles/${TAG}_bench_$c.json $c
+  timeout -k 10 400 python3 bench.py --full --config $c > $LOGS/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -5 $LOGS/bench_$c.log; exit 1; }
+  tail -1 $LOGS/bench_$c.log > $LOGS/${TAG}_bench_$c.json
+  python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], round(d['value']), round(r['kernel_ms'],1), 'frac', round(r['frac'],4), 'traffic/reactor', (r['traffic'] or 0)/d['config']['reactors_rank0'])" $LOGS/${TAG}_bench_$c.json $c
 done
 if [[ " $CFGS " == *" gri "* ]]; then
   # SQ instruction mix / VALU-busy counters (two passes) -> profiles/${TAG}_pmc_sq_gri.json
