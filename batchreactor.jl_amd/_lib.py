@@ -29,7 +29,7 @@ class Opts(C.Structure):
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_steps", C.c_int), ("device", C.c_int),
                 ("hmax", C.c_double), ("trace_cap", C.c_int), ("unstable_factor", C.c_double),
                 ("ignition_species", C.c_int), ("nout", C.c_int), ("tout", dp), ("yout", dp),
-                ("dq_jacobian", C.c_int)]
+                ("dq_jacobian", C.c_int), ("tout_per_reactor", C.c_int)]
 
 
 NSTAT = 20
@@ -49,7 +49,7 @@ EXPORTS = ["br_version", "br_last_error", "br_device_count", "br_mech_create", "
            "br_rates", "br_rhs", "br_jacobian", "br_integrate", "br_integrate_traced", "br_integrate_multi", "br_integrate_dev",
            "br_last_kernel_ms", "br_debug_lu_solve", "br_mech_parse", "br_host_mech_desc", "br_host_mech_sizes",
            "br_host_mech_species", "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml",
-           "br_integrate_host"]
+           "br_integrate_host", "br_phase_tout_dev", "br_integrate_phase"]
 
 # br_integrate_host callbacks: int f(void* user, double t, const double* u, double* du);
 # void cb(void* user, double t, const double* u)
@@ -83,6 +83,8 @@ def lib():
     L.br_integrate_traced.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.POINTER(Opts), dp, dp]
     L.br_integrate_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(Opts), vp, vp]
     L.br_integrate_multi.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(Opts), dp]
+    L.br_phase_tout_dev.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.br_integrate_phase.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.POINTER(Opts), dp, C.c_int, dp, dp, dp]
     L.br_last_kernel_ms.argtypes = [vp, dp]
     L.br_debug_lu_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, ip]
     L.br_debug_lu_solve.restype = C.c_int
@@ -100,7 +102,8 @@ def lib():
     for f in ("br_mech_create", "br_mech_destroy", "br_mech_info", "br_rates", "br_rhs", "br_jacobian",
               "br_integrate", "br_integrate_traced", "br_integrate_multi", "br_integrate_dev", "br_last_kernel_ms",
               "br_mech_parse", "br_host_mech_desc", "br_host_mech_sizes", "br_host_mech_species",
-              "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml", "br_integrate_host"):
+              "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml", "br_integrate_host",
+              "br_phase_tout_dev", "br_integrate_phase"):
         getattr(L, f).restype = C.c_int
     _lib = L
     return L

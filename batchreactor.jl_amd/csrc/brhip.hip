@@ -81,6 +81,40 @@ struct KOpts {
     int* work;                // k_integrate: persistent waves take reactor indices from this
                               // counter (nullptr: one reactor per wave, index = wave slot)
 };
+// Per-reactor output grids (br_opts.tout_per_reactor: tout[N][nout], one row per reactor, NaN = no output
+// as trailing padding) ride in bit 0 of KOpts::tout -- the array is 8-byte aligned -- and not in a field
+// or kernel argument of their own: either moves the kernel arguments, and that alone changed the
+// register allocation of kernels that never read it. tout is read only under the nout guards, so a
+// run without outputs never sees the tag.
+inline const double* tout_tag(const double* tout, bool per_reactor) {
+    return reinterpret_cast<const double*>(reinterpret_cast<size_t>(tout) | (per_reactor ? 1u : 0u));
+}
+// output time io of the reactor whose yout row index is orow = rid * nout + io: entry io of the shared
+// grid, or entry orow of the [N][nout] array (the index the yout row already needs)
+// (OPAQUE, the group engines: the wave-uniform tagged pointer goes through an opaque scalar copy at each
+// use. Without it the compiler decodes the tag once in k_group's prologue, outside the nout guards, and
+// the SGPRs that holds across the whole kernel, which is at the SGPR limit, shift its spills: the
+// no-output instruction stream then differs from the parent's in four times as many places. In the
+// wavefront and lane kernels the copy costs scratch instead, so they go without)
+template <bool OPAQUE>
+__device__ __forceinline__ size_t tout_bits(size_t b) {
+    if constexpr (OPAQUE) asm volatile("" : "+s"(b));
+    return b;
+}
+template <bool OPAQUE = false, class P>
+__device__ __forceinline__ double tout_at(P tagged, size_t orow, int io) {
+    const size_t b = tout_bits<OPAQUE>((size_t)tagged);
+    return reinterpret_cast<P>(b & ~(size_t)1)[(b & 1) ? orow : (size_t)io];
+}
+template <bool OPAQUE = false, class P>
+__device__ __forceinline__ bool tout_per_reactor(P tagged) { return (tout_bits<OPAQUE>((size_t)tagged) & 1) != 0; }
+// the preludes' test "output io is at t <= t0" (it gets u0). Shared grid: !(t > t0), as ever. Per-reactor
+// grid: t <= t0, which a NaN (no output) fails, so that the prelude writes no u0 for it and stops
+template <bool OPAQUE = false, class P>
+__device__ __forceinline__ bool tout_pre(P tagged, size_t orow, int io, double t0) {
+    const double t = tout_at<OPAQUE>(tagged, orow, io);
+    return tout_per_reactor<OPAQUE>(tagged) ? t <= t0 : !(t > t0);
+}
 
 // ------------------------------------------------------------------------------------
 // per-reactor LDS block: [Ctl: CVODE's cv_mem scalars][Vec: per-lane vectors][Smem: rate work]
@@ -364,10 +398,13 @@ __device__ __forceinline__ void dense_output(LCtl* C, VA<CPL, GW, VS>& V, const 
                                              double tlim) {
     int io = gui<GW>(C->iout);
     while (io < a.nout) {
-        const double t = guni<GW>(a.tout[io]);
+        // (per-reactor grids: the time sits at the yout row's own index, tout_at; a NaN there -- no
+        // output -- fails the comparison and ends this reactor's outputs for good)
+        const size_t orow = (size_t)a.rid * a.nout + io;
+        const double t = guni<GW>(tout_at<(GW < 64)>(a.tout, orow, io));
         if (!(t <= tlim)) break;
         const double sk = (t - tn) / h;
-        auto row = a.yout + ((size_t)a.rid * a.nout + io) * a.n;
+        auto row = a.yout + orow * a.n;
 #pragma unroll
         FOR_S {
             double yv = vget<CPL>(V, q, s);
@@ -1365,7 +1402,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     }
     if (o.nout) {                                           // outputs at t <= t0: the initial state
         int io = 0;
-        while (io < o.nout && !(o.tout[io] > t0)) {
+        while (io < o.nout && tout_pre(o.tout, (size_t)rid * o.nout + io, io, t0)) {
             if (!o.rid_t0)                                  // (a continued reactor wrote them already)
 #pragma unroll
                 FOR_S if (CS < n) o.yout[((size_t)rid * o.nout + io) * n + CS] = u0[s];
@@ -1582,6 +1619,20 @@ __global__ __launch_bounds__(256) void k_jac(DevMech M, int N, int rpb, const do
             for (int j = 0; j < M.n; ++j) row[j] = Jsave[j * col_rows(NMAX) + CS];
         }
     }
+}
+
+// br_phase_tout_dev: tout[i][j] = tau[j] * t_ign[i], NaN (no output) where t_ign is NaN or the product
+// is past tf[i]. One thread per entry; one rounded product, so the host mirror (phase_grid of the
+// Python package) gives the same bits.
+__global__ __launch_bounds__(256) void k_phase_tout(int N, const double* __restrict__ stats, int ntau,
+                                                    const double* __restrict__ tau, const double* __restrict__ tfv,
+                                                    double* __restrict__ tout) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)N * ntau) return;
+    const size_t i = e / ntau;
+    const int j = (int)(e - i * ntau);
+    const double p = tau[j] * stats[i * BR_NSTAT + 16];   // br_stats.t_ign
+    tout[e] = (p <= tfv[i]) ? p : NAN;
 }
 
 }  // namespace
@@ -2228,6 +2279,7 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
     o.nout = (opts && opts->nout > 0 && opts->tout && opts->yout) ? opts->nout : 0;
     o.tout = o.nout ? opts->tout : nullptr;
     o.yout = o.nout ? opts->yout : nullptr;
+    if (o.nout && opts->tout_per_reactor) o.tout = tout_tag(o.tout, true);
     o.dq_jac = (opts && opts->dq_jacobian) ? 1 : 0;
     o.defer_steps = o.max_steps;
     o.rid_list = nullptr;
@@ -2364,6 +2416,24 @@ int br_last_kernel_ms(br_mech* m, double* ms) {
     return 0;
 }
 
+// per-reactor output grids (br_opts.tout_per_reactor, host array tout[N][nout]): every row ascending,
+// NaN (no output) only as trailing padding; the message names the first bad reactor
+static int check_tout_rows(int N, int nout, const double* tout) {
+    for (int i = 0; i < N; ++i) {
+        const double* r = tout + (size_t)i * nout;
+        for (int j = 1; j < nout; ++j) {
+            if (r[j] != r[j]) continue;                     // padding, if nothing but NaN follows
+            if (r[j - 1] != r[j - 1])
+                return fail(BR_ERR_INPUT, "tout of reactor " + std::to_string(i) + ": NaN before a time (entry " +
+                                              std::to_string(j - 1) + "); NaN is trailing padding only");
+            if (!(r[j] >= r[j - 1]))
+                return fail(BR_ERR_INPUT, "tout of reactor " + std::to_string(i) + " must be ascending (entry " +
+                                              std::to_string(j) + ")");
+        }
+    }
+    return 0;
+}
+
 static int integrate_host(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                           const br_opts* opts, br_stats* stats, double* trace) {
     if (!m || N < 0 || !T || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
@@ -2375,7 +2445,13 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
     const size_t ntr = trace ? (size_t)N * (cap + 1) * (2 * n + 4) : 0;
     const int nout = (opts && opts->nout > 0 && opts->tout && opts->yout) ? opts->nout : 0;
     const size_t nyo = (size_t)N * nout * n;
-    const size_t nd = (size_t)N * (3 + n + BR_NSTAT) + ntr + nout + nyo;
+    const bool per = nout && opts->tout_per_reactor;       // tout[N][nout], one row per reactor
+    const size_t nto = per ? (size_t)N * nout : (size_t)nout;
+    if (per) {
+        int rc = check_tout_rows(N, nout, opts->tout);
+        if (rc) return rc;
+    }
+    const size_t nd = (size_t)N * (3 + n + BR_NSTAT) + ntr + nto + nyo;
     int rc = ensure_ws(m, nd * sizeof(double));
     if (rc) return rc;
     double* dT = (double*)m->ws;
@@ -2385,13 +2461,13 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
     double* dst = du_ + (size_t)N * n;
     double* dtr = dst + (size_t)N * BR_NSTAT;
     double* dto = dtr + ntr;
-    double* dyo = dto + nout;
+    double* dyo = dto + nto;
     br_opts od;
     if (opts) od = *opts;
     if (nout) {
-        for (int i = 1; i < nout; ++i)
+        for (int i = 1; i < nout && !per; ++i)
             if (!(opts->tout[i] >= opts->tout[i - 1])) return fail(BR_ERR_INPUT, "tout must be ascending");
-        HIPCHK(hipMemcpy(dto, opts->tout, nout * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dto, opts->tout, nto * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dyo, opts->yout, nyo * sizeof(double), hipMemcpyHostToDevice));
         od.tout = dto;
         od.yout = dyo;
@@ -2432,6 +2508,11 @@ int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, 
     }
     const int n = mechs[0]->n;
     const int nout = (opts && opts->nout > 0 && opts->tout && opts->yout) ? opts->nout : 0;
+    const bool per = nout && opts->tout_per_reactor;
+    if (per) {   // (here, so that the message names the reactor's index in the ensemble, not in its slice)
+        int rc0 = check_tout_rows(N, nout, opts->tout);
+        if (rc0) return rc0;
+    }
     std::vector<int> rc(ndev, 0);
     std::vector<std::string> msg(ndev);
     std::vector<std::thread> th;
@@ -2442,6 +2523,7 @@ int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, 
             br_opts od{};
             if (opts) od = *opts;
             if (nout) od.yout = opts->yout + (size_t)start * nout * n;
+            if (per) od.tout = opts->tout + (size_t)start * nout;
             rc[d] = integrate_host(mechs[d], cnt, T + start, Asv ? Asv + start : nullptr, u + (size_t)start * n,
                                    tf + start, opts ? &od : nullptr, stats ? stats + start : nullptr, nullptr);
             if (rc[d]) msg[d] = g_err;
@@ -2450,6 +2532,68 @@ int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, 
     for (auto& t : th) t.join();
     for (int d = 0; d < ndev; ++d)
         if (rc[d]) return fail(rc[d], "shard " + std::to_string(d) + ": " + msg[d]);
+    return 0;
+}
+
+int br_phase_tout_dev(int N, br_stats* dstats, int ntau, const double* dtau, const double* dtf, double* dtout,
+                      void* stream) {
+    if (N < 0 || ntau < 1 || !dstats || !dtau || !dtf || !dtout) return fail(BR_ERR_INPUT, "bad argument");
+    if (N == 0) return 0;
+    const size_t ne = (size_t)N * ntau;
+    hipLaunchKernelGGL(k_phase_tout, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N,
+                       (const double*)dstats, ntau, dtau, dtf, dtout);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
+                       const br_opts* opts, br_stats* stats, int ntau, const double* tau, double* tout, double* yout) {
+    if (!m || N < 0 || !T || !u || !tf || !tau || !tout || !yout || ntau < 1) return fail(BR_ERR_INPUT, "bad argument");
+    if (!opts || opts->ignition_species < 1 || opts->ignition_species > m->ng)
+        return fail(BR_ERR_INPUT, "br_integrate_phase needs br_opts.ignition_species (the phases are multiples of t_ign)");
+    for (int j = 0; j < ntau; ++j)
+        if (!(tau[j] > 0.0) || !(tau[j] < INFINITY) || (j && !(tau[j] >= tau[j - 1])))
+            return fail(BR_ERR_INPUT, "tau must be positive, finite and ascending");
+    if (N == 0) return 0;
+    HIPCHK(hipSetDevice(m->device));
+    const int n = m->n;
+    const size_t nu = (size_t)N * n, nto = (size_t)N * ntau, nyo = nto * n;
+    int rc = ensure_ws(m, ((size_t)N * (3 + BR_NSTAT) + 2 * nu + ntau + nto + nyo) * sizeof(double));
+    if (rc) return rc;
+    double* dT = (double*)m->ws;
+    double* dA = dT + N;
+    double* dtf = dA + N;
+    double* du_ = dtf + N;
+    double* du0 = du_ + nu;
+    double* dst = du0 + nu;
+    double* dtau = dst + (size_t)N * BR_NSTAT;
+    double* dto = dtau + ntau;
+    double* dyo = dto + nto;
+    HIPCHK(hipMemcpy(dT, T, N * sizeof(double), hipMemcpyHostToDevice));
+    if (Asv) HIPCHK(hipMemcpy(dA, Asv, N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtf, tf, N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(du0, u, nu * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtau, tau, ntau * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dyo, yout, nyo * sizeof(double), hipMemcpyHostToDevice));   // (rows without an output keep their values)
+    br_opts od = *opts;
+    od.trace_cap = 0;
+    // pass 1: no outputs, for t_ign
+    od.nout = 0; od.tout = nullptr; od.yout = nullptr; od.tout_per_reactor = 0;
+    HIPCHK(hipMemcpyAsync(du_, du0, nu * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+    rc = integrate_dev(m, N, dT, Asv ? dA : nullptr, du_, dtf, &od, (br_stats*)dst, nullptr, nullptr);
+    if (rc) return rc;
+    rc = br_phase_tout_dev(N, (br_stats*)dst, ntau, dtau, dtf, dto, nullptr);
+    if (rc) return rc;
+    // pass 2: the same u0 and options (the same steps) with the per-reactor grid
+    od.nout = ntau; od.tout = dto; od.yout = dyo; od.tout_per_reactor = 1;
+    HIPCHK(hipMemcpyAsync(du_, du0, nu * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+    rc = integrate_dev(m, N, dT, Asv ? dA : nullptr, du_, dtf, &od, (br_stats*)dst, nullptr, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(u, du_, nu * sizeof(double), hipMemcpyDeviceToHost));
+    if (stats) HIPCHK(hipMemcpy(stats, dst, (size_t)N * BR_NSTAT * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tout, dto, nto * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(yout, dyo, nyo * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -668,8 +668,9 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                     C->ign_x = mole_frac_of<1, GL>(uv, gl, o.ign);
                 }
                 if (o.nout) {                                           // outputs at t <= 0: the initial state
+                    // (inside rid < N: a group slot without a reactor forms no tout address)
                     int io = 0;
-                    while (io < o.nout && !(o.tout[io] > 0.0)) {
+                    while (io < o.nout && tout_pre<true>(o.tout, (size_t)rid * o.nout + io, io, 0.0)) {
                         if (act) o.yout[((size_t)rid * o.nout + io) * n + gl] = u0;
                         ++io;
                     }

@@ -717,8 +717,10 @@ __device__ __forceinline__ int l_post_solve(LCV& c, ZH<NM>& z, double (&acor)[NM
         c.ign_x = x; c.ign_t = c.tn;
     }
     const double tlim = fabs(c.tn - c.tstop) <= FUZZ * UROUND * (fabs(c.tn) + fabs(h)) ? c.tstop : c.tn;
-    while (c.iout < o.nout && o.tout[c.iout] <= tlim) {   // dense output (CVodeGetDky, CV_NORMAL)
-        const double sk = (o.tout[c.iout] - c.tn) / h;
+    // dense output (CVodeGetDky, CV_NORMAL); per-reactor grids: the lane's own row (tout_at), a NaN
+    // entry (no output) fails the comparison and ends the loop for good
+    while (c.iout < o.nout && tout_at(o.tout, (size_t)c.rid * o.nout + c.iout, c.iout) <= tlim) {
+        const double sk = (tout_at(o.tout, (size_t)c.rid * o.nout + c.iout, c.iout) - c.tn) / h;
         double zq[NM], yo[NM];
         z.row(q, zq);
 #pragma unroll
@@ -1151,7 +1153,7 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
                 c.hnewOK = 0; c.jcol = 0; c.pend = PEND_NONE; c.pflag = 0;
                 c.rid = rid; c.iout = 0; c.ign_t = 0.0; c.ign_rate = -INFINITY; c.t_ign = NAN; c.ign_dt = NAN;
                 c.ign_x = o.ign >= 0 ? l_mole_frac<NM>(y, n, o.ign) : 0.0;
-                while (c.iout < o.nout && !(o.tout[c.iout] > 0.0)) {   // outputs at t <= 0: u0
+                while (c.iout < o.nout && tout_pre(o.tout, (size_t)rid * o.nout + c.iout, c.iout, 0.0)) {   // outputs at t <= 0: u0
                     double* row = o.yout + ((size_t)rid * o.nout + c.iout) * n;
 #pragma unroll
                     for (int i = 0; i < NM; ++i) if (i < n) row[i] = y[i];

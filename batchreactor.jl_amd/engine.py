@@ -23,6 +23,34 @@ STAT_FIELDS = ("nsteps", "nfe", "nje", "nsetups", "nni", "ncfn", "netf", "status
 IGNITION_MARKER = "OH"   # the reference golden's ignition marker: max dX_OH/dt
 
 
+def output_grid(tout, N):
+    """The tout argument of the integrate calls as a C array: a 1-D grid shared by all reactors, or a
+    2-D [N, nout] array, row i the ascending output times of reactor i (br_opts.tout_per_reactor; NaN
+    = no output, trailing padding only). Returns (array or None, per_reactor). Raises ValueError for
+    any other shape, before the library is called."""
+    if tout is None:
+        return None, False
+    to = np.ascontiguousarray(tout, dtype=np.float64)
+    if to.ndim == 1:
+        return to, False
+    if to.ndim != 2 or to.shape[0] != N:
+        raise ValueError(f"tout must be [nout] or [N, nout] with N = {N}, got shape {to.shape}")
+    return to, True
+
+
+def phase_grid(t_ign, tau, tf):
+    """Per-reactor output grid at the ignition phases tau: tout[i, j] = tau[j] * t_ign[i], NaN (no
+    output) where t_ign[i] is NaN or the product exceeds tf[i]. tau ascending and positive, so the NaNs
+    of a row are trailing. Pure numpy; the CPU mirror of br_phase_tout_dev, bit for bit (one rounded
+    product per entry)."""
+    t_ign = np.atleast_1d(np.asarray(t_ign, dtype=np.float64))
+    tau = np.atleast_1d(np.asarray(tau, dtype=np.float64))
+    tf = np.broadcast_to(np.asarray(tf, dtype=np.float64), t_ign.shape)
+    p = t_ign[:, None] * tau[None, :]
+    with np.errstate(invalid="ignore"):
+        return np.where(p <= tf[:, None], p, np.nan)
+
+
 class Engine:
     def __init__(self, mech: Mechanism, device: int = 0):
         L = _lib.lib()
@@ -125,9 +153,10 @@ class Engine:
         return J
 
     def _opts(self, rtol, atol, max_steps, trace_cap=0, unstable_factor=0.0, tout=None, yout=None, dq_jacobian=False):
-        nout = 0 if tout is None else len(tout)
+        nout = 0 if tout is None else tout.shape[-1]   # tout: [nout], or [N, nout] (one row per reactor)
         return _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout,
-                         _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, int(dq_jacobian))
+                         _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, int(dq_jacobian),
+                         int(nout > 0 and tout.ndim == 2))
 
     def integrate(self, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, trace_cap=0, tout=None,
                   unstable_factor=0.0, dq_jacobian=False):
@@ -135,14 +164,16 @@ class Engine:
         trace[N, trace_cap+1, 2n+4] = (t, h, q, p_last, u[n], y_last[n]): u the accepted state, y_last
         and p_last the state and pressure of the step's last RHS evaluation (save_data semantics).
         With tout (ascending output times) the stats dict also carries "yout" [N, nout, n], the
-        states at those times (CVODE CV_NORMAL output, the step sequence is unchanged).
+        states at those times (CVODE CV_NORMAL output, the step sequence is unchanged). tout is one
+        1-D grid for all reactors or a 2-D [N, nout] array, row i reactor i's own grid (NaN = no output,
+        trailing padding only; rows of yout without an output stay 0).
         dq_jacobian: CVODE's difference-quotient Jacobian (the reference's setting), both engines."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
+        to, _ = output_grid(tout, N)
         T, A, tf = self._arr(T, N), self._arr(Asv, N), self._arr(tf, N)
         st = np.zeros((N, _lib.NSTAT))
-        to = None if tout is None else np.ascontiguousarray(tout, dtype=np.float64)
-        yo = None if tout is None else np.zeros((N, len(to), self.n))
+        yo = None if to is None else np.zeros((N, to.shape[-1], self.n))
         o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian)
         L = _lib.lib()
         if trace_cap > 0:
@@ -159,12 +190,65 @@ class Engine:
         return (u, stats, tr) if trace_cap > 0 else (u, stats)
 
     def integrate_device(self, T_ptr, Asv_ptr, u_ptr, tf_ptr, stats_ptr, N, stream_ptr=None, rtol=1e-6,
-                         atol=1e-10, max_steps=100000):
-        """Device-resident variant: raw device pointers (e.g. torch tensor data_ptr())."""
-        o = self._opts(rtol, atol, max_steps)
+                         atol=1e-10, max_steps=100000, tout_ptr=None, yout_ptr=None, nout=0, tout_per_reactor=False,
+                         dq_jacobian=False):
+        """Device-resident variant: raw device pointers (e.g. torch tensor data_ptr()). Dense output
+        with tout_ptr / yout_ptr / nout: device arrays tout [nout], or [N, nout] with tout_per_reactor
+        (e.g. what phase_tout_device built), and yout [N, nout, n]."""
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        if nout and tout_ptr and yout_ptr:
+            o.nout, o.tout_per_reactor = int(nout), int(bool(tout_per_reactor))
+            o.tout, o.yout = C.cast(C.c_void_p(tout_ptr), _lib.dp), C.cast(C.c_void_p(yout_ptr), _lib.dp)
         _lib.check(_lib.lib().br_integrate_dev(self.h, N, C.c_void_p(T_ptr), C.c_void_p(Asv_ptr),
                                                C.c_void_p(u_ptr), C.c_void_p(tf_ptr), C.byref(o),
                                                C.c_void_p(stats_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def integrate_phase(self, T, Asv, u0, tf, tau, rtol=1e-6, atol=1e-10, max_steps=100000, dq_jacobian=False):
+        """Ignition-phase sampling (br_integrate_phase): the states at t = tau[j] * t_ign[i], two passes
+        on the device from the same u0 (t_ign, then the outputs at the grid br_phase_tout_dev builds).
+        Returns (u, stats) as integrate, with stats["tout"] [N, ntau] (phase_grid(t_ign, tau, tf): NaN
+        where t_ign is unknown or the phase is past tf) and stats["yout"] [N, ntau, n] (rows of NaN
+        entries stay 0). Needs the ignition marker species in the mechanism."""
+        u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
+        N = u.shape[0]
+        tau = np.ascontiguousarray(np.atleast_1d(tau), dtype=np.float64)
+        if tau.ndim != 1 or tau.size == 0:
+            raise ValueError(f"tau must be a non-empty 1-D array, got shape {tau.shape}")
+        T, A, tf = self._arr(T, N), self._arr(Asv, N), self._arr(tf, N)
+        st = np.zeros((N, _lib.NSTAT))
+        to = np.zeros((N, tau.size))
+        yo = np.zeros((N, tau.size, self.n))
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        _lib.check(_lib.lib().br_integrate_phase(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),
+                                                 C.byref(o), _lib.dptr(st), tau.size, _lib.dptr(tau), _lib.dptr(to),
+                                                 _lib.dptr(yo)))
+        stats = {k: st[:, i] for i, k in enumerate(STAT_FIELDS)}
+        stats["tout"], stats["yout"] = to, yo
+        return u, stats
+
+    def phase_tout_device(self, stats, tau, tf, out=None, stream_ptr=None):
+        """br_phase_tout_dev on torch tensors of this engine's device: stats [N, NSTAT] as
+        integrate_device wrote it, tau [ntau] (ascending, positive), tf [N], all float64 and contiguous.
+        Returns tout [N, ntau] = tau[j] * t_ign[i] (NaN: t_ign unknown or past tf), a per-reactor grid
+        for br_integrate_dev; asynchronous on the stream (default: torch's current stream of the
+        tensors' device). br_phase_tout_dev selects no device itself, so the launch is made with the
+        tensors' device current."""
+        import torch
+        N, ntau = stats.shape[0], tau.shape[0]
+        for name, t, shape in (("stats", stats, (N, _lib.NSTAT)), ("tau", tau, (ntau,)), ("tf", tf, (N,))):
+            if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"{name}: contiguous float64 device tensor of shape {shape} expected")
+        if out is None:
+            out = torch.empty((N, ntau), dtype=torch.float64, device=stats.device)
+        elif tuple(out.shape) != (N, ntau) or out.dtype != torch.float64 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError(f"out: contiguous float64 device tensor of shape {(N, ntau)} expected")
+        with torch.cuda.device(stats.device):
+            if stream_ptr is None:
+                stream_ptr = torch.cuda.current_stream(stats.device).cuda_stream
+            _lib.check(_lib.lib().br_phase_tout_dev(N, C.c_void_p(stats.data_ptr()), ntau, C.c_void_p(tau.data_ptr()),
+                                                    C.c_void_p(tf.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(stream_ptr or 0)))
+        return out
 
     def last_kernel_ms(self):
         ms = np.zeros(1)
@@ -174,16 +258,17 @@ class Engine:
 
 def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, tout=None):
     """br_integrate_multi: the ensemble split into contiguous slices over `engines` (one Engine per
-    GPU, same mechanism), integrated concurrently; returns (u, stats) in ensemble order."""
-    L = _lib.lib()
+    GPU, same mechanism), integrated concurrently; returns (u, stats) in ensemble order. tout as
+    Engine.integrate: [nout], or [N, nout] for per-reactor grids (sliced with the ensemble)."""
     e0 = engines[0]
     u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
     N = u.shape[0]
+    to, _ = output_grid(tout, N)
     T, A, tf = e0._arr(T, N), e0._arr(Asv, N), e0._arr(tf, N)
     st = np.zeros((N, _lib.NSTAT))
-    to = None if tout is None else np.ascontiguousarray(tout, dtype=np.float64)
-    yo = None if tout is None else np.zeros((N, len(to), e0.n))
+    yo = None if to is None else np.zeros((N, to.shape[-1], e0.n))
     o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo)
+    L = _lib.lib()
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     _lib.check(L.br_integrate_multi(hs, len(engines), N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),
                                     C.byref(o), _lib.dptr(st)))

@@ -100,7 +100,8 @@ typedef struct br_opts {
                                  steps marks ignition (br_stats.t_ign; OH for the reference's
                                  ignition marker); 0 = not tracked                          */
     int nout;                 /* dense output: number of output times (0 = none)            */
-    const double* tout;       /* [nout] ascending output times, shared by all reactors; the
+    const double* tout;       /* [nout] ascending output times, shared by all reactors (or
+                                 [N][nout], one row per reactor, with tout_per_reactor); the
                                  state there is CVODE's CV_NORMAL output (CVodeGetDky(t, 0) on
                                  the step that passes t), the step sequence is unchanged     */
     double* yout;             /* [N][nout][n] states at tout (host memory for br_integrate,
@@ -110,6 +111,15 @@ typedef struct br_opts {
                                  the reference's CVODE_BDF() setting, src/BatchReactor.jl:140,
                                  :204), n extra RHS per Jacobian, in every engine (lane,
                                  group, wavefront); 0 (default): the analytic Jacobian       */
+    int tout_per_reactor;     /* 0 (default): tout is one grid [nout] shared by all reactors.
+                                 1: tout is [N][nout], row i the ascending output times of
+                                 reactor i (host memory for br_integrate, _traced and _multi,
+                                 device memory for br_integrate_dev); yout keeps its shape.
+                                 A NaN entry means "no output": allowed only as trailing
+                                 padding of a row (ragged grids), its yout rows are left
+                                 untouched, like rows with tout > tf[i]. The host entry points
+                                 check every row (BR_ERR_INPUT names the first bad reactor);
+                                 br_integrate_dev trusts the device array                    */
 } br_opts;
 
 #define BR_NSTAT 20
@@ -224,6 +234,29 @@ int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, 
  * ordered on one stream (or synchronised); concurrent integrations need one handle each. */
 int br_integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv, double* du,
                      const double* dtf, const br_opts* opts, br_stats* dstats, void* stream);
+
+/* ignition-phase output grid, built on the device (a small kernel on `stream`, asynchronous):
+ * dtout[i][j] = dtau[j] * dstats[i].t_ign, or NaN ("no output") where t_ign is NaN (not tracked, or
+ * the reactor failed before a step was accepted) or the product exceeds dtf[i]. dtau[ntau] ascending
+ * and positive, so the NaNs of a row are trailing: dtout[N][ntau] is a valid per-reactor grid for
+ * br_integrate_dev (br_opts.tout_per_reactor = 1, nout = ntau). All pointers are device memory; dstats
+ * is what an earlier br_integrate_dev on the same stream wrote (br_opts.ignition_species != 0). For
+ * device-resident ensembles: both passes run with no host round trip. The call takes no handle and
+ * selects no device: the device that owns `stream` and the arrays must be the caller's current one. */
+int br_phase_tout_dev(int N, br_stats* dstats /*read only*/, int ntau, const double* dtau, const double* dtf,
+                      double* dtout, void* stream);
+
+/* ignition-phase sampling, host buffers: the states at t = tau[j] * t_ign[i]. Two passes on the
+ * device from the same u0: pass 1 integrates without outputs for t_ign, br_phase_tout_dev builds
+ * the per-reactor grid, pass 2 integrates with it. The step sequence does not depend on the outputs,
+ * so pass 2's t_ign is pass 1's and every output sits at exactly the phase asked for. tau[ntau]
+ * ascending, positive and finite. Needs opts->ignition_species != 0 (else BR_ERR_INPUT);
+ * opts->nout / tout / yout / tout_per_reactor are ignored. u (in: u0, out: u(tf)) and stats are pass
+ * 2's, equal to a plain br_integrate's. tout[N][ntau] receives the grid (NaN = no output: t_ign
+ * unknown or tau[j] t_ign[i] > tf[i]); yout[N][ntau][n] rows of NaN entries are left untouched. */
+int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
+                       const br_opts* opts, br_stats* stats, int ntau, const double* tau,
+                       double* tout /*[N][ntau] out*/, double* yout /*[N][ntau][n] out*/);
 
 /* dense-solver check (tests): factor I - gamma_i*J_i with the engine's batched LU and solve
  * x_i = (I - gamma_i J_i)^-1 b_i. J[N][n][n] row-major; fail[i] = 0 or (k+1) for a zero pivot. */

@@ -51,16 +51,17 @@ struct BrOpts
     unstable_factor::Float64
     ignition_species::Cint      # 1-based gas species index (OH) for br_stats.t_ign; 0 = off
     nout::Cint
-    tout::Ptr{Float64}          # [nout] ascending output times
+    tout::Ptr{Float64}          # [nout] ascending output times ([nout x N] with tout_per_reactor)
     yout::Ptr{Float64}          # [N][nout][n]
     dq_jacobian::Cint           # 1: CVODE's DQ Jacobian (cvLsDenseDQJac, the reference's setting), every engine
+    tout_per_reactor::Cint      # 1: tout is [nout x N], column i reactor i's own ascending grid (NaN = no output, trailing only)
 end
 # dq_jacobian=true selects CVODE's difference-quotient Jacobian, the reference's CVODE_BDF() setting
 # (src/BatchReactor.jl:140,:204); the default is the analytic Jacobian
 BrOpts(; rtol=1e-6, atol=1e-10, max_steps=100_000, device=0, hmax=0.0, unstable_factor=0.0, ignition_species=0,
-       dq_jacobian::Bool=false) =
+       dq_jacobian::Bool=false, tout_per_reactor::Bool=false) =
     BrOpts(rtol, atol, Cint(max_steps), Cint(device), Float64(hmax), Cint(0), Float64(unstable_factor),
-           Cint(ignition_species), Cint(0), C_NULL, C_NULL, Cint(dq_jacobian))
+           Cint(ignition_species), Cint(0), C_NULL, C_NULL, Cint(dq_jacobian), Cint(tout_per_reactor))
 
 # br_stats rows of the [NSTAT x N] matrix returned below
 const STAT_FIELDS = (:nsteps, :nfe, :nje, :nsetups, :nni, :ncfn, :netf, :status, :cyc_total, :cyc_rhs, :cyc_jac,
@@ -97,12 +98,43 @@ function integrate_traced!(m::Ptr{Cvoid}, T, Asv, u::Matrix{Float64}, tf; cap::I
     stats = zeros(NSTAT, N)
     trace = zeros(2n + 4, cap + 1, N)
     o = BrOpts(opts.rtol, opts.atol, opts.max_steps, opts.device, opts.hmax, Cint(cap), opts.unstable_factor,
-               opts.ignition_species, Cint(0), C_NULL, C_NULL, opts.dq_jacobian)
+               opts.ignition_species, Cint(0), C_NULL, C_NULL, opts.dq_jacobian, Cint(0))
     check(ccall((:br_integrate_traced, lib), Cint,
                 (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BrOpts}, Ptr{Float64},
                  Ptr{Float64}), m, N, T, Asv, u, tf, Ref(o), stats, trace))
     return stats, trace
 end
+
+"""Ignition-phase sampling (br_integrate_phase): the states at t = tau[j] * t_ign[i]. Two passes on the
+device from the same u0: the first for t_ign, the second with the per-reactor output grid built from
+it (the step sequence does not depend on the outputs, so every output sits at exactly the phase asked
+for). `opts.ignition_species` must be set. `u` (n x N) is overwritten with the end states. Returns
+(stats [NSTAT x N], tout [ntau x N], yout [n x ntau x N]); tout is NaN where t_ign is unknown or the
+phase is past tf, and the yout columns of those entries stay 0."""
+function integrate_phase!(m::Ptr{Cvoid}, T::Vector{Float64}, Asv::Vector{Float64}, u::Matrix{Float64},
+                          tf::Vector{Float64}, tau::Vector{Float64}; opts::BrOpts=BrOpts())
+    n, N = size(u)
+    ntau = length(tau)
+    stats = zeros(NSTAT, N)
+    tout = zeros(ntau, N)
+    yout = zeros(n, ntau, N)
+    check(ccall((:br_integrate_phase, lib), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BrOpts}, Ptr{Float64},
+                 Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                m, N, T, Asv, u, tf, Ref(opts), stats, ntau, tau, tout, yout))
+    return stats, tout, yout
+end
+
+"""The grid integrate_phase! uses, for device-resident ensembles (br_phase_tout_dev): all pointers are
+device memory (e.g. AMDGPU.jl arrays) on the handle's device, `dstats` [NSTAT x N] as br_integrate_dev
+wrote it; `dtout` [ntau x N] is then a per-reactor grid for br_integrate_dev (tout_per_reactor=true).
+Asynchronous on `stream` (a hipStream_t, C_NULL = the default stream); the device of the arrays
+and the stream must be the caller's current device (the call selects none)."""
+phase_tout_dev!(dtout::Ptr{Float64}, N::Integer, dstats::Ptr{Float64}, ntau::Integer, dtau::Ptr{Float64},
+                dtf::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:br_phase_tout_dev, lib), Cint,
+                (Cint, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                N, dstats, ntau, dtau, dtf, dtout, stream))
 
 # ---------------------------------------------------------------------------------------------
 # host mechanism compiler and batch.xml reader of libbrhip.so (C++; br_mech_parse, br_read_batch_xml):
@@ -361,9 +393,11 @@ end
 
 """batch_reactor_ensemble: N independent reactors, each with its own T, p, inlet composition and
 end time, in one call (one br_integrate over the ensemble). Returns (x_end [ng x N], theta_end
-[ns x N], stats [NSTAT x N], including t_ign from the OH marker)."""
+[ns x N], stats [NSTAT x N], including t_ign from the OH marker). With `phase=tau` every reactor is
+also sampled at the ignition phases t = tau[j] * t_ign[i] (integrate_phase!) and the call returns
+(x_end, theta_end, stats, tout [ntau x N], yout [n x ntau x N])."""
 function batch_reactor_ensemble(md::DeviceMech, T::AbstractVector, p::AbstractVector, comps::AbstractVector,
-                                tf; Asv=1.0, rtol::Real=1e-6, atol::Real=1e-10)
+                                tf; Asv=1.0, rtol::Real=1e-6, atol::Real=1e-10, phase=nothing)
     N = length(T)
     U = zeros(ncomp(md), N)
     for i in 1:N
@@ -371,6 +405,12 @@ function batch_reactor_ensemble(md::DeviceMech, T::AbstractVector, p::AbstractVe
     end
     fillv(v) = v isa AbstractVector ? collect(Float64, v) : fill(Float64(v), N)
     opts = BrOpts(rtol=rtol, atol=atol, ignition_species=ignition_species(md))
+    if phase !== nothing
+        stats, tout, yout = integrate_phase!(md.m, collect(Float64, T), fillv(Asv), U, fillv(tf),
+                                             collect(Float64, phase); opts=opts)
+        X = reduce(hcat, [state_to_molefrac(md, U[:, i]) for i in 1:N])
+        return X, U[md.ng+1:end, :], stats, tout, yout
+    end
     stats = integrate!(md.m, collect(Float64, T), fillv(Asv), U, fillv(tf); opts=opts)
     X = reduce(hcat, [state_to_molefrac(md, U[:, i]) for i in 1:N])
     return X, U[md.ng+1:end, :], stats
@@ -521,6 +561,6 @@ function batch_reactor(input_file::AbstractString, lib_dir::AbstractString, user
 end
 
 export batch_reactor, batch_reactor_ensemble, compile_mechanism, read_batch_xml, DeviceMech, Chemistry,
-       UserDefinedState, BrOpts, retcode_symbol, integrate_host
+       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!
 
 end # module
