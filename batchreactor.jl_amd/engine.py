@@ -152,6 +152,18 @@ class Engine:
         _lib.check(_lib.lib().br_jacobian(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(J)))
         return J
 
+    def group_eval(self, T, Asv, u):
+        """(du, J) as the group integrator of this mechanism evaluates them (br_debug_group_eval: the
+        device functions, LDS blocks and global slots of k_group); du [N, n], J [N, n, n] as jacobian()"""
+        u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
+        N = u.shape[0]
+        T, A = self._arr(T, N), self._arr(Asv, N)
+        du = np.zeros_like(u)
+        J = np.zeros((N, self.n, self.n))
+        _lib.check(_lib.lib().br_debug_group_eval(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(du),
+                                                  _lib.dptr(J)))
+        return du, J
+
     def _opts(self, rtol, atol, max_steps, trace_cap=0, unstable_factor=0.0, tout=None, yout=None, dq_jacobian=False):
         nout = 0 if tout is None else tout.shape[-1]   # tout: [nout], or [N, nout] (one row per reactor)
         return _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout,

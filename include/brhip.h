@@ -262,6 +262,20 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
  * x_i = (I - gamma_i J_i)^-1 b_i. J[N][n][n] row-major; fail[i] = 0 or (k+1) for a zero pivot. */
 int br_debug_lu_solve(int N, int n, const double* J, const double* gamma, const double* b, double* x, int* fail);
 
+/* group-engine check (tests): RHS and analytic Jacobian as the group integrator evaluates them,
+ * through the device functions, workgroup shape, LDS blocks and global slots of the instance
+ * br_integrate would launch for this mechanism (BR_ERR_UNSUPPORTED when it has none, n > 32). At most
+ * two workgroups: each group evaluates its reactors one after another in the same block and slot.
+ * du[N][n]; J[N][n][n] row-major, d(du_i)/d(u_j), as br_jacobian. Asv may be NULL (1.0). */
+int br_debug_group_eval(br_mech* m, int N, const double* T, const double* Asv, const double* u, double* du, double* J);
+
+/* group-engine check (tests): the register-resident LU and solve of the group integrator instance
+ * (gl, nm) = (16, 9), (16, 16), (32, 24) or (32, 32), n <= nm (else BR_ERR_INPUT). Arguments as
+ * br_debug_lu_solve; matrix i sits in group i mod (64 / gl) of its wave. perm[N][n]: the original row
+ * at each row position after the interchanges; fail[i] = 0 or (k+1) for a zero pivot (x_i = 0 then). */
+int br_debug_group_lu_solve(int gl, int nm, int N, int n, const double* J, const double* gamma, const double* b,
+                            double* x, int* fail, int* perm);
+
 /* User-defined chemistry: replaces solve(ODEProblem(residual!, u0, (0, tf), params), CVODE_BDF();
  * reltol, abstol, save_everystep=false, callback=FunctionCallingCallback(save_data)) with the userchem
  * residual! (src/BatchReactor.jl:51-54,:197-200,:204-210,:358-360,:371-372). The user's RHS is host

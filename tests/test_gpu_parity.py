@@ -329,7 +329,8 @@ def test_programmatic_api(pkg, gpu):
 @pytest.mark.parametrize("n", [9, 20, 53, 66, 72])
 def test_batched_lu_solve(pkg, gpu, n):
     """The integrator's row-per-lane LU (partial pivoting, no row swaps) + solve against numpy on
-    random, ill-scaled Newton matrices I - gamma J (fp64; 1e-12 backward-error bound)."""
+    random, ill-scaled Newton matrices I - gamma J (fp64; 1e-12 backward-error bound); then with
+    singular matrices in between: the zero-pivot flag k + 1 (as denseGETRF)."""
     import ctypes as C
     rng = np.random.default_rng(n)
     N = 64
@@ -343,6 +344,27 @@ def test_batched_lu_solve(pkg, gpu, n):
                              f.ctypes.data_as(C.POINTER(C.c_int)))
     assert rc == 0 and np.all(f == 0)
     for i in range(N):
+        A = np.eye(n) - g[i] * J[i]
+        res = A @ x[i] - b[i]
+        assert np.max(np.abs(res)) <= 1e-12 * (np.abs(A).sum(1).max() * np.abs(x[i]).max() + np.abs(b[i]).max())
+    # the zero-pivot flag: column k of I - gamma J exactly zero (gamma = 0.5, J[:, k] = 2 e_k) gives
+    # fail = k + 1; the matrices in between are as above
+    ks = (0, n // 2, n - 1)
+    sing = {}
+    for c, i in enumerate(range(1, N, 3)):
+        k = ks[c % 3]
+        g[i] = 0.5
+        J[i, :, k] = 0.0
+        J[i, k, k] = 2.0
+        sing[i] = k
+    rc = L.br_debug_lu_solve(N, n, pkg._lib.dptr(J), pkg._lib.dptr(g), pkg._lib.dptr(b), pkg._lib.dptr(x),
+                             f.ctypes.data_as(C.POINTER(C.c_int)))
+    assert rc == 0
+    for i in range(N):
+        if i in sing:
+            assert f[i] == sing[i] + 1, (i, f[i], sing[i])
+            continue
+        assert f[i] == 0, (i, f[i])
         A = np.eye(n) - g[i] * J[i]
         res = A @ x[i] - b[i]
         assert np.max(np.abs(res)) <= 1e-12 * (np.abs(A).sum(1).max() * np.abs(x[i]).max() + np.abs(b[i]).max())

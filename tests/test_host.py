@@ -243,6 +243,62 @@ def test_native_compiler_tables_bit_identical(pkg, gas, surf, gasphase):
     np.testing.assert_array_equal(nat["theta0"], m.theta0)
 
 
+# the group-eligible falloff mechanisms tests/test_group_kernels.py generates: n, gas reactions, and
+# the counts of (Lindemann, Troe, +M, irreversible) reactions in each. The 12-species list of
+# s12+ch4ni holds one Troe reaction (2OH(+M)<=>H2O2(+M)) and no irreversible one (both of GRI's that
+# are left in s16 consume CH3).
+_SUBSET_CONTENTS = {"s16": (16, 60, 1, 4, 6, 2), "s24": (24, None, 1, None, 6, None),
+                    "s32": (32, 186, None, None, 6, 6), "s12+ch4ni": (25, None, 1, 1, 5, 0)}
+
+
+@pytest.mark.parametrize("key", list(_SUBSET_CONTENTS))
+@pytest.mark.parametrize("troe3", [False, True], ids=["troe4", "troe3"])
+def test_generated_falloff_mechanisms(pkg, tmp_path, key, troe3):
+    """The GRI-Mech subsets written by test_group_kernels.subset_mechanism are what the group-engine
+    tests need: n <= 32 components, Lindemann, Troe (4 parameters; 3 for the first Troe reaction with
+    the troe3 option), +M and (where the species list leaves one) irreversible reactions, at most 32
+    distinct efficiency rows (the group species block holds 32 third-body sums); and br_mech_parse
+    compiles them to the Python compiler's tables bit for bit."""
+    from test_group_kernels import SUBSETS, subset_mechanism
+    species, surf = SUBSETS[key]
+    d = subset_mechanism(tmp_path, species, troe3=troe3, surface=surf)
+    m = pkg.Mechanism.from_files(d, gas_mech="mech.dat", surface_mech=surf)
+    t = m.tables
+    n, nrg, n_lind, n_troe, n_tb, n_irr = _SUBSET_CONTENTS[key]
+    assert m.n == n and m.ng == len(species) and m.gas_species == species
+    fo = t["g_tb"] == 2
+    lind = int(np.sum(fo & (t["g_troe_n"] == 0)))
+    troe4 = int(np.sum(fo & (t["g_troe_n"] == 4)))
+    troe3_ = int(np.sum(fo & (t["g_troe_n"] == 3)))
+    irr = int(np.sum(t["g_rev"] == 0))
+    assert lind + troe4 + troe3_ == int(fo.sum())
+    assert nrg is None or m.nrg == nrg
+    assert lind >= 1 and (n_lind is None or lind == n_lind)
+    assert troe3_ == int(troe3) and troe4 + troe3_ >= 1 and (n_troe is None or troe4 + troe3_ == n_troe)
+    assert troe4 >= 1 or key == "s12+ch4ni"
+    assert int(np.sum(t["g_tb"] == 1)) == n_tb
+    assert (irr >= 1 or key == "s12+ch4ni") and (n_irr is None or irr == n_irr)
+    rows = {t["g_eff"][r].tobytes() for r in np.flatnonzero(t["g_tb"] != 0)}
+    assert 1 <= len(rows) <= 32
+    if troe3:
+        r = int(np.flatnonzero(fo & (t["g_troe_n"] > 0))[0])
+        assert t["g_troe_n"][r] == 3 and t["g_troe"][r, 3] == 0.0
+    rc, nat = _native(pkg, os.path.join(d, "mech.dat"), surf)
+    assert rc == 0, nat
+    assert nat["sizes"] == (m.ng, m.ns, m.nrg, m.nrs) and nat["names"] == m.species
+    py = dict(t, molwt=m.molwt, nasa=m.nasa, sigma=m.sigma)
+    for f in _DESC_SHAPES:
+        a, b = nat[f], np.asarray(py[f])
+        if a is None:
+            assert b.size == 0, f
+        elif a.dtype.kind == "f":
+            assert a.shape == b.shape, f
+            assert np.array_equal(a.view(np.uint64), np.ascontiguousarray(b, np.float64).view(np.uint64)), f
+        else:
+            assert a.shape == b.shape and np.array_equal(a, b), f
+    np.testing.assert_array_equal(nat["theta0"], m.theta0)
+
+
 def test_native_compiler_errors(pkg, tmp_path):
     """Bad inputs come back as BR_ERR_INPUT with a message (no exception crosses the C-ABI)."""
     rc, msg = _native(pkg, "nonexistent.dat")
