@@ -1,6 +1,6 @@
 // brhip_lane.hpp -- ONE REACTOR PER LANE integrator for small gas-phase mechanisms
 // (n <= 12 components, no surface species; e.g. H2/O2, n = 9, the C2 ensemble).
-// Included by brhip.hip inside its anonymous namespace: it uses that file's CVODE constants,
+// Included by brhip.hip inside its anonymous namespace: it uses the CVODE constants of brhip_ctl.hpp,
 // KOpts, inv_int, root_int and pow_int.
 //
 // Why a second engine: with n = 9 a wave-per-reactor layout leaves 55 of 64 lanes idle in the

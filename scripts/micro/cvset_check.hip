@@ -1,8 +1,8 @@
 // cvset_check.hip -- device-side check that the 16-lane groups' lane-parallel cvSet (cv_set_lp) and
 // step-size ratios give bit-for-bit the values of the generic forms (cv_set<16>, one root_int per
-// ratio) on random controller states. Includes the whole integrator translation unit; not part of
+// ratio) on random controller states. Includes the controller header alone; not part of
 // libbrhip.so.   python3 scripts/cvset_check.py
-#include "../../batchreactor.jl_amd/csrc/brhip.hip"
+#include "../../batchreactor.jl_amd/csrc/brhip_ctl.hpp"   // (includes brhip_device.hpp)
 
 namespace {
 constexpr int NOUT = 16;   // doubles per case and variant

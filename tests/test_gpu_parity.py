@@ -326,7 +326,7 @@ def test_programmatic_api(pkg, gpu):
     assert t[-1] == 10.0 and abs(sum(xd.values()) - 1) < 1e-12
 
 
-@pytest.mark.parametrize("n", [9, 20, 53, 66, 72])
+@pytest.mark.parametrize("n", [9, 20, 53, 60, 66, 72])   # k_lu_check<16 | 32 | 56 | 64>, k_lu_check2<72> (twice)
 def test_batched_lu_solve(pkg, gpu, n):
     """The integrator's row-per-lane LU (partial pivoting, no row swaps) + solve against numpy on
     random, ill-scaled Newton matrices I - gamma J (fp64; 1e-12 backward-error bound); then with
@@ -962,6 +962,38 @@ def test_group_engine_register_widths(pkg, orc, gpu, monkeypatch, tmp_path, n, e
     Uw, sw = eng.integrate(T, Asv, U0, 1e-2, rtol=1e-10, atol=1e-16)
     assert np.all(sw["status"] == 0)
     assert max(close_states(Ug[i], Uw[i], rtol=1e-6, floor=1e-14) for i in range(N)) <= 1.0
+
+
+@pytest.mark.parametrize("which,engine,kernel", [("h2o2+3", "lane", "k_lane<12>"), ("gri47+ni", "wave", "k_integrate<64>")])
+def test_remaining_integrator_instances(pkg, orc, gpu, monkeypatch, tmp_path, which, engine, kernel):
+    """The two integrator instances no bench or golden mechanism reaches: k_lane<12> (H2/O2 plus three
+    inert species, n = 12) and k_integrate<64> (GRI-Mech without six species + the Ni surface mechanism,
+    n = 47 + 13 = 60, one component per lane with surface chemistry). Eight reactors each, the bars of
+    test_integrate_parity_tight: rtol 1e-10 / atol 1e-16 on both sides, end states at tf = 1e-2 s to
+    1e-6 relative (floor 1e-14)."""
+    if which == "h2o2+3":
+        d, surf, case = _h2o2_with_inerts(tmp_path, 12), None, "h2o2"
+    else:
+        from test_group_kernels import subset_mechanism
+        gri = pkg.Mechanism.from_files(LIB, gas_mech="grimech.dat").gas_species
+        species = [s for s in gri if s not in ("AR", "C3H7", "C3H8", "CH2CHO", "CH3CHO", "HCNO")]
+        d, surf, case = subset_mechanism(tmp_path, species, surface="ch4ni.xml"), "ch4ni.xml", "gas_surf"
+    pm = pkg.Mechanism.from_files(d, gas_mech="mech.dat", surface_mech=surf)
+    om = orc.Mech(os.path.join(d, "mech.dat"), os.path.join(d, "therm.dat"), os.path.join(d, surf) if surf else None,
+                  conv=orc.CONV_REFERENCE)
+    assert pm.n == (12 if which == "h2o2+3" else 60)
+    monkeypatch.setenv("BRHIP_ENGINE", engine)
+    eng = pkg.Engine(pm)
+    assert eng.engine == engine and eng.kernel_name == kernel, (eng.engine, eng.kernel_name)
+    N, tf = 8, 1e-2
+    T, Asv, U0 = _ignition_inputs(pm, case, N, 6)
+    U, st = eng.integrate(T, Asv, U0, tf, rtol=1e-10, atol=1e-16)
+    assert np.all(st["status"] == 0)
+    Uo, so, bad = om.integrate_batch(T, Asv, U0, tf, rtol=1e-10, atol=1e-16, analytic_jac=True, nthreads=8)
+    assert bad == 0 and all(s["status"] == 0 for s in so)
+    for i in range(N):
+        e = close_states(U[i], Uo[i], rtol=1e-6, floor=1e-14)
+        assert e <= 1.0, (which, i, e)
 
 
 def test_lane_engine_deferral(pkg, orc, gpu, monkeypatch):

@@ -311,6 +311,224 @@ def test_native_compiler_errors(pkg, tmp_path):
     assert rc == -10 and "unknown species 'XX'" in L.br_last_error().decode()
 
 
+# --------------------------------------------------------------------------------------------
+# the table packer of br_mech_create (csrc/mech_pack.cpp) through csrc/mech_pack_dump: plain host code
+# --------------------------------------------------------------------------------------------
+_PACK_DUMP = os.path.join(ROOT, "batchreactor.jl_amd", "mech_pack_dump")
+_PACK_TABLES = ("img", "nasa", "g_par", "g_dnu", "fo_par", "s_par", "tb_eff", "col_ptr", "col_rx")
+_NI_GAS = "CH4 H2O H2 CO CO2 O2 N2"
+# case -> (gas mechanism or the key of a generated GRI subset, surface mechanism, gasphase, flags)
+_PACK_FILE_CASES = {"gri": ("grimech.dat", None, None), "h2o2": ("h2o2.dat", None, None),
+                    "ni": (None, "ch4ni.xml", _NI_GAS), "gri+ni": ("grimech.dat", "ch4ni.xml", None)}
+_PACK_CASES = {k: v + ((),) for k, v in _PACK_FILE_CASES.items()}
+_PACK_CASES.update({k: (k, None, None, ()) for k in ("s16", "s24", "s32", "s12+ch4ni")})
+_PACK_CASES.update({"gri/no-spread": ("grimech.dat", None, None, ("--no-spread",)),
+                    "gri+ni/no-spread": ("grimech.dat", "ch4ni.xml", None, ("--no-spread",)),
+                    "gri/no-jfast": ("grimech.dat", None, None, ("--no-jfast",))})
+
+
+def _pack_files(tmp_path, case):
+    """(directory, gas, surface, gasphase, flags) of a _PACK_CASES entry; the GRI subsets are written
+    into tmp_path (troe3 off)"""
+    gas, surf, gasphase, flags = _PACK_CASES[case]
+    if gas in ("s16", "s24", "s32", "s12+ch4ni"):
+        from test_group_kernels import SUBSETS, subset_mechanism
+        species, surf = SUBSETS[gas]
+        return str(subset_mechanism(tmp_path, species, troe3=False, surface=surf)), "mech.dat", surf, None, flags
+    return LIB, gas, surf, gasphase, flags
+
+
+def _pack_dump(exe, tmp_path, case):
+    """run the dump program on a case: ({table: bytes}, {scalar: text})"""
+    d, gas, surf, gasphase, flags = _pack_files(tmp_path, case)
+    out = tmp_path / "packed"
+    out.mkdir()
+    path = lambda f: os.path.join(d, f) if f else "-"
+    cmd = [exe, *flags, str(out), os.path.join(d, "therm.dat"), path(gas), path(surf)] + ([gasphase] if gasphase else [])
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    tables = {t: (out / f"{t}.bin").read_bytes() for t in _PACK_TABLES}
+    scalars = dict(ln.split("=", 1) for ln in (out / "devmech.txt").read_text().split())
+    return tables, scalars
+
+
+@pytest.mark.parametrize("case", list(_PACK_CASES))
+def test_packed_tables_match_golden(tmp_path, case):
+    """mech_pack's tables and DevMech scalars are, bit for bit, what br_mech_create uploaded before the
+    packer was split out of it (tests/golden/packed_tables.json: SHA-256 of every table, recorded from
+    that br_mech_create) -- GRI, H2/O2, surface-only Ni, GRI + Ni, the four generated falloff subsets,
+    and the BRHIP_SPREAD=0 / BRHIP_JFAST=0 forms of GRI (and GRI + Ni)."""
+    import hashlib
+    import json
+    want = json.load(open(os.path.join(GOLDEN, "packed_tables.json")))[case]
+    tables, scalars = _pack_dump(_PACK_DUMP, tmp_path, case)
+    assert scalars == want["scalars"]
+    assert {t: hashlib.sha256(b).hexdigest() for t, b in tables.items()} == want["sha256"]
+
+
+def _scatter_list(w):
+    """decode a 4-word net-stoichiometry list: [(species, nu)] in slot order"""
+    cnt = int(w[3]) >> 24
+    out = []
+    for t in range(cnt):
+        off = (int(w[t >> 1]) >> (16 * (t & 1))) & 0xffff
+        nu = (int(w[3]) >> (4 * t)) & 15
+        assert off % 8 == 0
+        out.append((off // 8, nu - 16 if nu >= 8 else nu))
+    return out
+
+
+def _net_stoich(reac, prod):
+    """[(species, nu != 0)] in order of first appearance (reactants, then products)"""
+    order, nu = [], {}
+    for k, v in [(int(k), -1) for k in reac] + [(int(k), 1) for k in prod]:
+        if k not in nu:
+            order.append(k)
+        nu[k] = nu.get(k, 0) + v
+    return [(k, nu[k]) for k in order if nu[k]]
+
+
+@pytest.mark.parametrize("case", list(_PACK_FILE_CASES) + ["gri/no-spread", "gri+ni/no-spread"])
+def test_packed_tables_decode_to_the_mechanism(pkg, tmp_path, case):
+    """The dumped tables, decoded here with numpy from the formats of csrc/brhip_layout.hpp, say what the
+    br_mech_desc tables say: every scatter list is its reaction's net stoichiometry (at most 6 entries,
+    none with nu = 0; with --no-spread in first-appearance order), the RX records are in the permuted
+    order falloff, +M, elementary with their reactants, products and flags, col_ptr / col_rx list exactly
+    the reactions whose rate depends on each component, and the image sections are 16-byte aligned and
+    disjoint."""
+    gas, surf, gasphase, flags = _PACK_CASES[case]
+    rc, d = _native(pkg, gas, surf, gasphase)
+    assert rc == 0, d
+    tables, sc = _pack_dump(_PACK_DUMP, tmp_path, case)
+    M = {k: int(v) for k, v in sc.items() if k not in ("p_std", "G")}
+    ng, ns, nrg, nrs = d["sizes"]
+    n = ng + ns
+    assert (M["ng"], M["ns"], M["n"], M["nrg"], M["nrs"]) == (ng, ns, n, nrg, nrs) and M["cpl"] == (2 if n > 64 else 1)
+    spw = 80 if M["cpl"] == 2 else 64
+    img = tables["img"]
+    assert len(img) == M["img_bytes"]
+    # ---- image sections
+    cmp_ = np.frombuffer(img, np.int32, n + 1, M["cmp_off"]) if M["jfast"] else None
+    tjp = np.frombuffer(img, np.int32, n + 1, M["tjp_off"]) if M["jfast"] else None
+    sections = [(0, 16 * spw), (16 * spw, 32 * nrg), (M["sx_off"], 48 * nrs), (M["sxe_off"], 64 * nrs),
+                (M["tbe_off"], 16 * M["ntbe"]), (M["tbs_off"], 4 * M["nset"])]
+    if M["jfast"]:
+        sections += [(M["cmp_off"], 4 * (n + 1)), (M["cmr_off"], 2 * int(cmp_[n])), (M["tjp_off"], 4 * (n + 1)),
+                     (M["tje_off"], 16 * int(tjp[n]))]
+    assert M["jfast"] == (1 if case in ("gri", "h2o2", "gri/no-spread") else 0)
+    end = 0
+    for off, size in sections:                                # in image order
+        assert off % 16 == 0 and off >= end, (off, end)
+        end = off + size
+    assert end <= M["img_bytes"] and M["img_bytes"] % 16 == 0
+    mw = np.frombuffer(img, np.float64, 2 * spw, 0)
+    np.testing.assert_array_equal(mw[:ng], d["molwt"])
+    if ns:
+        np.testing.assert_array_equal(mw[spw + ng:spw + n], d["sigma"])
+    # ---- gas reactions: permuted order, records, scatter lists
+    perm = [r for p in (2, 1, 0) for r in range(nrg) if d["g_tb"][r] == p] if nrg else []
+    ra = np.frombuffer(img, np.uint32, 8 * nrg, 16 * spw)
+    spread = "--no-spread" not in flags
+    for i, r in enumerate(perm):
+        w = np.concatenate([ra[4 * i:4 * i + 4], ra[4 * nrg + 4 * i:4 * nrg + 4 * i + 4]])
+        nf, nr = int(d["g_nf"][r]), int(d["g_nr"][r])
+        info = int(w[2])
+        assert (info & 7, (info >> 3) & 7, (info >> 6) & 1, (info >> 7) & 3) == (nf, nr, int(d["g_rev"][r] != 0), int(d["g_tb"][r]))
+        assert [(int(w[0]) >> 8 * e) & 255 for e in range(4)] == [int(k) for k in d["g_f"][r][:nf]] + [spw] * (4 - nf)
+        assert [(int(w[1]) >> 8 * e) & 255 for e in range(4)] == [int(k) for k in d["g_r"][r][:nr]] + [spw] * (4 - nr)
+        got, net = _scatter_list(w[4:8]), _net_stoich(d["g_f"][r][:nf], d["g_r"][r][:nr])
+        assert len(got) <= 6 and (sorted(got) == sorted(net) if spread else got == net), (r, got, net)
+    tb_seq = [(int(ra[4 * i + 2]) >> 7) & 3 for i in range(nrg)]
+    assert tb_seq == sorted(tb_seq, reverse=True) and tb_seq.count(2) == M["nfo"] and len(tb_seq) - tb_seq.count(0) == M["ntb"]
+    # ---- surface reactions
+    sx = np.frombuffer(img, np.uint32, 12 * nrs, M["sx_off"])
+    for r in range(nrs):
+        w = sx[12 * r:12 * r + 12]
+        nf, np_ = int(d["s_nf"][r]), int(d["s_np"][r])
+        info = int(w[4])
+        assert (info & 7, (info >> 3) & 7, (info >> 6) & 1, (info >> 7) & 7) == (nf, np_, int(d["s_stick"][r] != 0), int(d["s_ncov"][r]))
+        got, net = _scatter_list(w[6:10]), _net_stoich(d["s_f"][r][:nf], d["s_p"][r][:np_])
+        assert len(got) <= 6 and (sorted(got) == sorted(net) if spread else got == net), (r, got, net)
+    # ---- Jacobian column lists
+    col_ptr = np.frombuffer(tables["col_ptr"], np.int32)
+    col_rx = np.frombuffer(tables["col_rx"], np.int32)
+    assert len(col_ptr) == n + 1 and col_ptr[0] == 0 and len(col_rx) == max(int(col_ptr[n]), 1)
+    for j in range(n):
+        want = [i for i, r in enumerate(perm)
+                if j in d["g_f"][r][:d["g_nf"][r]] or j in d["g_r"][r][:d["g_nr"][r]]
+                or (d["g_tb"][r] and j < ng and d["g_eff"][r][j] != 0.0)]
+        want += [nrg + r for r in range(nrs)
+                 if j in d["s_f"][r][:d["s_nf"][r]] or j in d["s_cov_sp"][r][:d["s_ncov"][r]]]
+        assert list(col_rx[col_ptr[j]:col_ptr[j + 1]]) == want, j
+
+
+def _tiny_desc(pkg, ng=3, ns=0, gas=(), surf=(), eff=None):
+    """hand-made br_mech_desc: gas = [(reactants, products, tb)], surf = [(reactants, products, stick, ncov)]
+    (species indices; rate constants and thermodynamics are zeros: the packer only copies them)"""
+    keep = []
+    nrg, nrs = len(gas), len(surf)
+
+    def arr(a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return pkg._lib.dptr(a) if dt == np.float64 else pkg._lib.iptr(a)
+
+    def padded(rows, w):
+        out = np.full((max(len(rows), 1), w), -1, np.int32)
+        for i, r in enumerate(rows):
+            out[i, :min(len(r), w)] = r[:w]
+        return out
+
+    z = lambda *s: np.zeros(s if s[0] else (1,) + s[1:])
+    g_eff = np.ones((max(nrg, 1), ng)) if eff is None else np.asarray(eff, float)
+    desc = pkg._lib.MechDesc(
+        ng, ns, nrg, nrs, 0, 1e5, arr(np.ones(ng), np.float64), arr(z(ng, 15), np.float64),
+        arr([len(g[0]) for g in gas] or [0], np.int32), arr([len(g[1]) for g in gas] or [0], np.int32),
+        arr(padded([g[0] for g in gas], 4), np.int32), arr(padded([g[1] for g in gas], 4), np.int32),
+        arr([1] * max(nrg, 1), np.int32), arr([g[2] for g in gas] or [0], np.int32),
+        arr(z(nrg, 3), np.float64), arr(z(nrg, 3), np.float64), arr([0] * max(nrg, 1), np.int32),
+        arr(z(nrg, 4), np.float64), arr(g_eff, np.float64),
+        1e-9, arr(np.ones(max(ns, 1)), np.float64),
+        arr([len(s[0]) for s in surf] or [0], np.int32), arr([len(s[1]) for s in surf] or [0], np.int32),
+        arr(padded([s[0] for s in surf], 6), np.int32), arr(padded([s[1] for s in surf], 6), np.int32),
+        arr([s[2] for s in surf] or [0], np.int32), arr(z(nrs, 3), np.float64),
+        arr([s[3] for s in surf] or [0], np.int32), arr(np.zeros((max(nrs, 1), 4), np.int32), np.int32),
+        arr(z(nrs, 4), np.float64))
+    return desc, keep
+
+
+@pytest.mark.parametrize("kw,code,msg", [
+    (dict(ng=6, gas=[([0, 1, 2, 3, 4], [5], 0)]), -30, "reaction with >4 entries"),
+    (dict(ng=8, gas=[([0, 1, 2, 3], [4, 5, 6, 7], 0)]), -30, "reaction touches more than 6 species"),
+    (dict(ng=2, ns=8, surf=[([0, 2, 3, 4, 5, 6, 7], [1], 0, 0)]), -30, "surface reaction too large"),
+    (dict(ng=2, ns=2, surf=[([2], [3], 0, 5)]), -30, "surface reaction too large"),
+    (dict(ng=2, ns=8, surf=[([0, 2, 3, 4], [1, 5, 6, 7], 0, 0)]), -30, "surface reaction touches more than 6 species"),
+    (dict(ng=2, ns=2, surf=[([2], [3], 1, 0)]), -10, "sticking reaction without gas reactant"),
+    (dict(ng=66, gas=[([0], [1], 1)] * 65, eff=1.0 + np.eye(65, 66)), -30, "more than 64 third-body efficiency sets"),
+    (dict(ng=70, ns=3), -30, "n > 72 components is not supported by this build"),
+])
+def test_packer_errors(pkg, kw, code, msg):
+    """Every size limit of the packer (and br_mech_create's own n > 72) comes back from br_mech_create as
+    its error code and message, before any device call: reached here from hand-made descriptions."""
+    L = pkg._lib.lib()
+    desc, keep = _tiny_desc(pkg, **kw)
+    h = ctypes.c_void_p()
+    assert L.br_mech_create(ctypes.byref(desc), 0, ctypes.byref(h)) == code
+    assert L.br_last_error().decode() == msg
+
+
+def test_packer_under_host_sanitizers(tmp_path):
+    """The mechanism compiler and the packer, built with -fsanitize=address,undefined as a program of
+    their own (make sanitize-dump) and run on the four file mechanisms: a clean exit each."""
+    csrc = os.path.join(ROOT, "batchreactor.jl_amd", "csrc")
+    r = subprocess.run(["make", "-s", "-C", csrc, "sanitize-dump", f"SANDIR={tmp_path}"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    for i, case in enumerate(_PACK_FILE_CASES):
+        sub = tmp_path / f"c{i}"
+        sub.mkdir()
+        _pack_dump(str(tmp_path / "mech_pack_dump_san"), sub, case)
+
+
 @pytest.mark.parametrize("case", ["batch_h2o2", "batch_ch4", "batch_surf", "batch_gas_and_surf", "batch_udf"])
 def test_native_batch_xml(pkg, case):
     """br_read_batch_xml reads the five reference scenario inputs as the Python reader does
