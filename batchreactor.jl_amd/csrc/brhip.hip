@@ -68,7 +68,7 @@ __host__ __device__ constexpr int br_wpe(int nmax) {
 template <int NMAX>
 __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_per_eu(br_wpe(NMAX), 8))) void k_integrate(
     DevMech M, int N, int rpb, const double* __restrict__ Tv, const double* __restrict__ Asvv, double* __restrict__ U,
-    const double* __restrict__ tfv, KOpts o, double* __restrict__ stats, double* __restrict__ Jws,
+    const double* __restrict__ tfv, KOpts o, br_stats* __restrict__ stats, double* __restrict__ Jws,
     double* __restrict__ trace) {
     constexpr int CPL = NMAX > 64 ? 2 : 1;   // components per lane
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -143,17 +143,23 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     C->dq_mininc = 1.0; C->nfe_dq = 0;
     if (o.ign >= 0) C->ign_x = uni(mole_frac_of<CPL>(u0, lane, o.ign));
     // counters and ignition marker of the lane pass (deferred reactors) to continue from
-    double st_in[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    enum { P_NSTEPS, P_NFE, P_NJE, P_NSETUPS, P_NNI, P_NCFN, P_NETF, P_NFE_DQ, P_COUNT };
+    double prev[P_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (o.rid_t0 && stats) {
+        // (read as columns of the [N][BR_NSTAT] array, index rid * BR_NSTAT + column, the seven leading
+        // counters in one loop: as member reads the same loads left k_integrate<32> and <72> with another
+        // register allocation)
+        static_assert(BR_STAT_COL(nsteps) == P_NSTEPS && BR_STAT_COL(netf) == P_NETF, "the carried counters lead br_stats");
+        const double* last = reinterpret_cast<const double*>(stats);
 #pragma unroll
-        for (int k = 0; k < 7; ++k) st_in[k] = uni(stats[(size_t)rid * BR_NSTAT + k]);
-        st_in[7] = uni(stats[(size_t)rid * BR_NSTAT + 19]);   // nfe_dq
+        for (size_t k = BR_STAT_COL(nsteps); k <= BR_STAT_COL(netf); ++k) prev[k] = uni(last[(size_t)rid * BR_NSTAT + k]);
+        prev[P_NFE_DQ] = uni(last[(size_t)rid * BR_NSTAT + BR_STAT_COL(nfe_dq)]);
         // the step limit is on the whole run (SciML maxiters): the lane pass's steps count against it
-        C->a_max_steps = max(o.max_steps - (int)st_in[0], 0);
+        C->a_max_steps = max(o.max_steps - (int)prev[P_NSTEPS], 0);
         if (o.ign >= 0) {
-            C->ign_rate = uni(stats[(size_t)rid * BR_NSTAT + 17]);
-            C->t_ign = uni(stats[(size_t)rid * BR_NSTAT + 16]);
-            C->ign_dt = uni(stats[(size_t)rid * BR_NSTAT + 18]);
+            C->ign_rate = uni(last[(size_t)rid * BR_NSTAT + BR_STAT_COL(ign_rate)]);
+            C->t_ign = uni(last[(size_t)rid * BR_NSTAT + BR_STAT_COL(t_ign)]);
+            C->ign_dt = uni(last[(size_t)rid * BR_NSTAT + BR_STAT_COL(ign_dt)]);
         }
     }
     if (o.nout) {                                           // outputs at t <= t0: the initial state
@@ -167,24 +173,13 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         C->iout = io;
     }
 
-#if BR_ASM_MARKS   // analysis builds: phase markers in the ISA listing (they are scheduling barriers)
-#define BR_CLK(v) asm volatile("; BR_PHASE_BEGIN " #v)
-#define BR_ACC(acc, v) asm volatile("; BR_PHASE_END " #acc)
-#elif BR_PHASE_CLOCKS
-    unsigned long long cyc_rhs = 0, cyc_jac = 0, cyc_lu = 0, cyc_sol = 0, cyc_ctl = 0;
-    const unsigned long long clk0 = clock64();
-#define BR_CLK(v) const unsigned long long v = clock64()
-#define BR_ACC(acc, v) acc += clock64() - v
-#else
-#define BR_CLK(v)
-#define BR_ACC(acc, v)
-#endif
+    BR_CLK_BEGIN;
     const unsigned long long cyc0 = wall_clock64();
     int perm[CPL];
 #pragma unroll
     FOR_S perm[s] = CS;
     LDSd* scr = (LDSd*)(S.sp + Lay<CPL>::ACCW);   // solve / LU scratch: the production sums are idle then
-    double* p_last = reinterpret_cast<double*>(W.rbase);   // Ctl::p_last is the first field
+    double* p_last = reinterpret_cast<double*>(W.rbase);
     int dqj = -1;   // >= 0: building DQ Jacobian column dqj (this RHS is at y + inc_dqj e_dqj)
     for (;;) {
         double y[CPL], f[CPL];
@@ -269,20 +264,15 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         if (CS < n) U[(size_t)rid * n + CS] = u_out;
     }
     if (stats && lane == 0) {
-        double* st = stats + (size_t)rid * BR_NSTAT;
-        st[0] = st_in[0] + ui(C->nst); st[1] = st_in[1] + ui(C->nfe); st[2] = st_in[2] + ui(C->nje);
-        st[3] = st_in[3] + ui(C->nsetups); st[4] = st_in[4] + ui(C->nni); st[5] = st_in[5] + ui(C->ncfn);
-        st[6] = st_in[6] + ui(C->netf); st[7] = (double)status;
-        st[8] = (double)(wall_clock64() - cyc0);
-#if BR_PHASE_CLOCKS
-        st[9] = (double)cyc_rhs; st[10] = (double)cyc_jac; st[11] = (double)cyc_lu; st[12] = (double)cyc_sol;
-        st[14] = (double)cyc_ctl; st[15] = (double)(clock64() - clk0);
-#else
-        st[9] = st[10] = st[11] = st[12] = st[14] = st[15] = 0.0;
-#endif
-        st[13] = ud(C->tn);
-        st[16] = o.ign >= 0 ? ud(C->t_ign) : NAN; st[17] = o.ign >= 0 ? ud(C->ign_rate) : NAN;
-        st[18] = o.ign >= 0 ? ud(C->ign_dt) : NAN; st[19] = st_in[7] + ui(C->nfe_dq);
+        br_stats& s = stats[rid];
+        s.nsteps = prev[P_NSTEPS] + ui(C->nst); s.nfe = prev[P_NFE] + ui(C->nfe); s.nje = prev[P_NJE] + ui(C->nje);
+        s.nsetups = prev[P_NSETUPS] + ui(C->nsetups); s.nni = prev[P_NNI] + ui(C->nni); s.ncfn = prev[P_NCFN] + ui(C->ncfn);
+        s.netf = prev[P_NETF] + ui(C->netf); s.status = (double)status;
+        s.cyc_total = (double)(wall_clock64() - cyc0);
+        BR_CLK_STORE(s);
+        s.t_end = ud(C->tn);
+        s.t_ign = o.ign >= 0 ? ud(C->t_ign) : NAN; s.ign_rate = o.ign >= 0 ? ud(C->ign_rate) : NAN;
+        s.ign_dt = o.ign >= 0 ? ud(C->ign_dt) : NAN; s.nfe_dq = prev[P_NFE_DQ] + ui(C->nfe_dq);
     }
     }   // next reactor
 }
@@ -380,14 +370,14 @@ __global__ __launch_bounds__(256) void k_jac(DevMech M, int N, int rpb, const do
 // br_phase_tout_dev: tout[i][j] = tau[j] * t_ign[i], NaN (no output) where t_ign is NaN or the product
 // is past tf[i]. One thread per entry; one rounded product, so the host mirror (phase_grid of the
 // Python package) gives the same bits.
-__global__ __launch_bounds__(256) void k_phase_tout(int N, const double* __restrict__ stats, int ntau,
+__global__ __launch_bounds__(256) void k_phase_tout(int N, const br_stats* __restrict__ stats, int ntau,
                                                     const double* __restrict__ tau, const double* __restrict__ tfv,
                                                     double* __restrict__ tout) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)N * ntau) return;
     const size_t i = e / ntau;
     const int j = (int)(e - i * ntau);
-    const double p = tau[j] * stats[i * BR_NSTAT + 16];   // br_stats.t_ign
+    const double p = tau[j] * stats[i].t_ign;
     tout[e] = (p <= tfv[i]) ? p : NAN;
 }
 
@@ -397,10 +387,19 @@ __global__ __launch_bounds__(256) void k_phase_tout(int N, const double* __restr
 // host side
 // ------------------------------------------------------------------------------------
 // the kernel instances, one lookup per family (the kernels are emitted in the order of these functions)
-// the group-engine instances (brhip_group.hpp)
+// the group-engine instances (brhip_group.hpp; also of the test kernels of brhip_debug.hpp): f(GL, NM)
+// as integral constants for the built pair (gl, nm), nullptr for any other
+template <class F>
+static const void* grp_instance(int gl, int nm, F f) {
+    using std::integral_constant;
+    if (gl == 16 && nm == 9) return f(integral_constant<int, 16>{}, integral_constant<int, 9>{});
+    if (gl == 16 && nm == 16) return f(integral_constant<int, 16>{}, integral_constant<int, 16>{});
+    if (gl == 32 && nm == 24) return f(integral_constant<int, 32>{}, integral_constant<int, 24>{});
+    if (gl == 32 && nm == 32) return f(integral_constant<int, 32>{}, integral_constant<int, 32>{});
+    return nullptr;
+}
 static const void* grp_kernel(int gl, int nm) {
-    if (gl == 16) return nm == 9 ? (const void*)k_group<16, 9> : (const void*)k_group<16, 16>;
-    return nm == 24 ? (const void*)k_group<32, 24> : (const void*)k_group<32, 32>;
+    return grp_instance(gl, nm, [](auto g, auto w) { return (const void*)k_group<g(), w()>; });
 }
 static const void* wave_kernel(int nmax) {   // one reactor per wavefront
     return nmax == 16 ? (const void*)k_integrate<16> : nmax == 32 ? (const void*)k_integrate<32>
@@ -586,7 +585,7 @@ int br_mech_create(const br_mech_desc* d, int device, br_mech** out) {
     std::unique_ptr<br_mech, int (*)(br_mech*)> owner(new br_mech(), br_mech_destroy);   // frees on every early return
     br_mech* m = owner.get();
     m->device = device; m->ng = ng; m->ns = ns; m->nrg = nrg; m->nrs = nrs; m->n = n;
-    m->nmax = n <= 16 ? 16 : (n <= 32 ? 32 : (n <= 56 ? 56 : (n <= 64 ? 64 : 72)));
+    m->nmax = nmax_of(n);
     m->dm = pk.dm;
     DevMech& M = m->dm;
     int rc = 0;
@@ -1007,7 +1006,7 @@ int br_phase_tout_dev(int N, br_stats* dstats, int ntau, const double* dtau, con
     if (N == 0) return 0;
     const size_t ne = (size_t)N * ntau;
     hipLaunchKernelGGL(k_phase_tout, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N,
-                       (const double*)dstats, ntau, dtau, dtf, dtout);
+                       (const br_stats*)dstats, ntau, dtau, dtf, dtout);
     HIPCHK(hipGetLastError());
     return 0;
 }

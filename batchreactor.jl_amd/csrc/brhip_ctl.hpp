@@ -1,6 +1,7 @@
 // brhip_ctl.hpp -- the CVODE controller of the integrator kernels on the per-reactor LDS block: Ctl, VA,
 // cv_set / cv_set_lp, ctl_post_rhs, ctl_post_solve and the difference-quotient Jacobian helpers (dq_*),
-// with the CVODE constants and the kernel options (KOpts) they share with the three engines.
+// with the CVODE constants, the kernel options (KOpts) and the phase-clock macros (BR_CLK / BR_ACC)
+// they share with the three engines.
 // Included by brhip.hip (first) and by scripts/micro/cvset_check.hip.
 #pragma once
 #include "../../include/brhip.h"
@@ -11,6 +12,49 @@
 #define BR_PHASE_CLOCKS 0   // per-phase shader-clock counters in br_stats (diagnostic build: libbrhip_diag.so)
 #endif
 #include "brhip_device.hpp"
+// Phase clocks of the three engines, one set of macros. A reactor's accumulators (cyc_rhs, cyc_jac, cyc_lu,
+// cyc_sol, cyc_ctl) and the origin of its cyc_clk: BR_CLK_BEGIN declares and starts them in one go
+// (k_integrate, inside its reactor loop); the persistent loops of the group and lane engines declare
+// them once (BR_CLK_VARS) and restart them per reactor (BR_CLK_START()). BR_CLK(v) opens an interval,
+// BR_ACC(acc, v) adds it to acc, BR_CLK_STORE(s) writes the clock columns of br_stats s. Product build: no
+// accumulators, zeros stored. Diagnostic build: shader clocks. Analysis builds (BR_ASM_MARKS): phase
+// markers in the ISA listing instead (they are scheduling barriers).
+#if BR_PHASE_CLOCKS
+#define BR_CLK_BEGIN                                                                      \
+    unsigned long long cyc_rhs = 0, cyc_jac = 0, cyc_lu = 0, cyc_sol = 0, cyc_ctl = 0;    \
+    const unsigned long long cyc_all = clock64()
+#define BR_CLK_VARS unsigned long long cyc_rhs = 0, cyc_jac = 0, cyc_lu = 0, cyc_sol = 0, cyc_ctl = 0, cyc_all = 0
+#define BR_CLK_START() do { cyc_rhs = cyc_jac = cyc_lu = cyc_sol = cyc_ctl = 0; cyc_all = clock64(); } while (0)
+#define BR_CLK_STORE(s)                                                                                            \
+    do {                                                                                                           \
+        (s).cyc_rhs = (double)cyc_rhs; (s).cyc_jac = (double)cyc_jac; (s).cyc_lu = (double)cyc_lu;                 \
+        (s).cyc_sol = (double)cyc_sol; (s).cyc_ctl = (double)cyc_ctl; (s).cyc_clk = (double)(clock64() - cyc_all); \
+    } while (0)
+#define BR_CLK_VALUES (PhaseClk{cyc_rhs, cyc_jac, cyc_lu, cyc_sol, cyc_ctl, cyc_all})
+#else
+#define BR_CLK_BEGIN
+#define BR_CLK_VARS
+#define BR_CLK_START()
+#define BR_CLK_STORE(s) (s).cyc_rhs = (s).cyc_jac = (s).cyc_lu = (s).cyc_sol = (s).cyc_ctl = (s).cyc_clk = 0.0
+#define BR_CLK_VALUES (PhaseClk{})
+#endif
+// the accumulators by value, for a stats writer outside the kernel's scope (l_store_stats)
+struct PhaseClk {
+    unsigned long long cyc_rhs, cyc_jac, cyc_lu, cyc_sol, cyc_ctl, cyc_all;
+    __device__ __forceinline__ void store(br_stats& s) const { BR_CLK_STORE(s); }
+};
+// column of a br_stats field in a [N][BR_NSTAT] array of doubles
+#define BR_STAT_COL(f) (offsetof(br_stats, f) / sizeof(double))
+#if BR_ASM_MARKS
+#define BR_CLK(v) asm volatile("; BR_PHASE_BEGIN " #v)
+#define BR_ACC(acc, v) asm volatile("; BR_PHASE_END " #acc)
+#elif BR_PHASE_CLOCKS
+#define BR_CLK(v) const unsigned long long v = clock64()
+#define BR_ACC(acc, v) acc += clock64() - v
+#else
+#define BR_CLK(v)
+#define BR_ACC(acc, v)
+#endif
 // Diagnostic-only instruction-count experiments (scripts/micro/exp_hooks.hpp: a phase run twice,
 // extra VALU or memory work per Newton iteration) attach at these points of k_integrate; the
 // product build leaves them empty.
@@ -134,6 +178,8 @@ struct Ctl {
     double* a_yout;
     int a_max_steps, a_trace_cap, a_rid, a_n, a_ign, a_nout;
 };
+// (the RHS takes the start of a reactor's LDS block as its p_last)
+static_assert(offsetof(Ctl, p_last) == 0, "Ctl::p_last is the first field of a reactor's LDS block");
 constexpr int CTL_BYTES = (sizeof(Ctl) + 15) / 16 * 16;
 enum { V_Z0 = 0, V_ACOR = QMAX + 1, V_EWT, V_TEMP, V_Y, NVEC };   // z0..z5, acor, ewt, tempv, y
 // V[vec * 64 + lane] for the first component slot. Two components per lane (n = 65..72): slot 1 of

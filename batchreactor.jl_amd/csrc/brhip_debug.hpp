@@ -87,7 +87,7 @@ struct DevScratch {
 extern "C" int br_debug_lu_solve(int N, int n, const double* J, const double* gamma, const double* b, double* x,
                                  int* fail_out) {
     if (N <= 0 || n <= 0 || n > 72) return fail_code_input();
-    const int nmax = n <= 16 ? 16 : (n <= 32 ? 32 : (n <= 56 ? 56 : (n <= 64 ? 64 : 72)));
+    const int nmax = nmax_of(n);
     double *dJ, *dg, *db, *dx, *dws;
     int* df;
     DevScratch S;
@@ -122,27 +122,7 @@ template <int GL, int NM>
 __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL == 16 ? BR_QWPE : BR_QWPE32))) void k_group_eval(
     DevMech M, int N, const double* __restrict__ Tv, const double* __restrict__ Asvv, const double* __restrict__ U,
     double* __restrict__ DU, double* __restrict__ Jout, double* __restrict__ Jws) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    stage_tables(M, smem_raw);
-    const Tab tb = tab_view<1>(smem_raw, M);
-    constexpr int GPW = 64 / GL;
-    const int lane = threadIdx.x & 63, gl = lane & (GL - 1);
-    const int grp = (int)(threadIdx.x / GL);
-    const int slot = blockIdx.x * (BR_QWPB * GPW) + grp;
-    const int RB = grp::block_bytes(GL, NM, MF(nrg), MF(nfo), MF(nrs));
-    char* rbase = smem_raw + M.img_bytes + (size_t)grp * RB;
-    double* sp = reinterpret_cast<double*>(rbase + grp::sp_off(GL, NM));
-    double* fod = reinterpret_cast<double*>(rbase + grp::fod_off(GL, NM, MF(nrg), MF(nrs)));
-    double* skd = fod + 4 * MF(nfo);
-    const int SD = grp::slot_doubles(GL, MF(nrg));
-    QKd* kd = launder(Jws) + (size_t)slot * SD + GL * GL;
-    const __amdgpu_buffer_rsrc_t jrs = __builtin_amdgcn_make_buffer_rsrc((void*)launder(Jws), (short)0, 0x7fffffff, 0x00020000);
-    const unsigned jvo = (unsigned)(slot * SD + gl) * 8u;
-    auto jst = [&](int j, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), jrs, jvo, j * (GL * 8), 0); };
-    auto jld = [&](int j) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(jrs, jvo, j * (GL * 8), 0)); };
-    const int n = MF(n);
-    const bool asv_fixed = (MF(conv) & 4) != 0;
-    double* p_last = reinterpret_cast<double*>(rbase);                  // Ctl::p_last is the first field
+    GRP_CONTEXT(M, Jws);
     const int G = (int)gridDim.x * (BR_QWPB * GPW);
     for (int rid = slot;; rid += G) {
         if (__ballot(rid < N) == 0) break;
@@ -223,8 +203,7 @@ extern "C" int br_debug_group_eval(br_mech* m, int N, const double* T, const dou
     HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
     if (Asv) HIPCHK(hipMemcpy(dA, Asv, (size_t)N * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
-    const void* fn = GL == 16 ? (NM == 9 ? (const void*)k_group_eval<16, 9> : (const void*)k_group_eval<16, 16>)
-                              : (NM == 24 ? (const void*)k_group_eval<32, 24> : (const void*)k_group_eval<32, 32>);
+    const void* fn = grp_instance(GL, NM, [](auto g, auto w) { return (const void*)k_group_eval<g(), w()>; });
     HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->grp_shmem));
     const DevMech dm = m->dm;
     const double* pA = Asv ? dA : nullptr;
@@ -238,8 +217,8 @@ extern "C" int br_debug_group_eval(br_mech* m, int N, const double* T, const dou
 
 extern "C" int br_debug_group_lu_solve(int gl, int nm, int N, int n, const double* J, const double* gamma, const double* b,
                                        double* x, int* fail_out, int* perm) {
-    const bool built = (gl == 16 && (nm == 9 || nm == 16)) || (gl == 32 && (nm == 24 || nm == 32));
-    if (!built || N <= 0 || n <= 0 || n > nm || !J || !gamma || !b || !x || !fail_out || !perm) return fail_code_input();
+    const void* fn = grp_instance(gl, nm, [](auto g, auto w) { return (const void*)k_group_lu<g(), w()>; });
+    if (!fn || N <= 0 || n <= 0 || n > nm || !J || !gamma || !b || !x || !fail_out || !perm) return fail_code_input();
     double *dJ, *dg, *db, *dx, *dws;
     int *df, *dp;
     DevScratch S;
@@ -254,8 +233,6 @@ extern "C" int br_debug_group_lu_solve(int gl, int nm, int N, int n, const doubl
     HIPCHK(hipMemcpy(dg, gamma, (size_t)N * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db, b, (size_t)N * n * 8, hipMemcpyHostToDevice));
     const int gpb = BR_QWPB * (64 / gl);
-    const void* fn = gl == 16 ? (nm == 9 ? (const void*)k_group_lu<16, 9> : (const void*)k_group_lu<16, 16>)
-                              : (nm == 24 ? (const void*)k_group_lu<32, 24> : (const void*)k_group_lu<32, 32>);
     void* args[] = {(void*)&N, (void*)&n, (void*)&dJ, (void*)&dg, (void*)&db, (void*)&dx, (void*)&df, (void*)&dp, (void*)&dws};
     HIPCHK(hipLaunchKernel(fn, dim3((N + gpb - 1) / gpb), dim3(64 * BR_QWPB), args, 0, 0));
     HIPCHK(hipMemcpy(x, dx, (size_t)N * n * 8, hipMemcpyDeviceToHost));

@@ -564,38 +564,46 @@ __device__ __forceinline__ int g_post_solve(LCtl* C, VA<1, GL, VS>& V, int gl, d
                     // spilled) vs 159.1k at 2; the wavefront engine does 217.7k, round 4)
 #endif
 
+// A group's view of its workgroup, as the locals of a <GL, NM> kernel (k_group and the test kernel
+// k_group_eval: one layout for both): the staged tables `tb`, the lane within the group `gl`, the group's
+// workspace slot `slot`, its LDS block `rbase` = [Ctl | V | species block sp | fod | skd] (p_last: its
+// start, Ctl::p_last) and its global slot [saved J | kd]. The saved J goes through a buffer resource:
+// lane offset in a VGPR (jvo), the column offset j GL 8 as the instruction's scalar offset (jst, jld; as
+// 64-bit addresses, the columns past 4 KB of a 32-lane slot were materialised per column, hoisted out of
+// the loop and spilled). A macro and not a struct: as members of a returned or constructed object the
+// same values lost their address flags and changed the register allocation of both kernels.
+#define GRP_CONTEXT(M, Jws)                                                                                          \
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];                                                  \
+    stage_tables(M, smem_raw);                                                                                       \
+    const Tab tb = tab_view<1>(smem_raw, M);                                                                         \
+    constexpr int GPW = 64 / GL;                                        /* groups per wave */                        \
+    const int lane = threadIdx.x & 63, gl = lane & (GL - 1);                                                         \
+    const int grp = (int)(threadIdx.x / GL);                            /* group within the workgroup */             \
+    const int slot = blockIdx.x * (BR_QWPB * GPW) + grp;                                                             \
+    const int RB = grp::block_bytes(GL, NM, MF(nrg), MF(nfo), MF(nrs));                                              \
+    char* rbase = smem_raw + M.img_bytes + (size_t)grp * RB;                                                         \
+    double* sp = reinterpret_cast<double*>(rbase + grp::sp_off(GL, NM));                                             \
+    double* fod = reinterpret_cast<double*>(rbase + grp::fod_off(GL, NM, MF(nrg), MF(nrs)));                         \
+    double* skd = fod + 4 * MF(nfo);                                                                                 \
+    const int SD = grp::slot_doubles(GL, MF(nrg));                      /* global doubles per group slot */          \
+    QKd* kd = launder(Jws) + (size_t)slot * SD + GL * GL;                                                            \
+    const __amdgpu_buffer_rsrc_t jrs = __builtin_amdgcn_make_buffer_rsrc((void*)launder(Jws), (short)0, 0x7fffffff, 0x00020000); \
+    const unsigned jvo = (unsigned)(slot * SD + gl) * 8u;                                                            \
+    auto jst = [&](int j, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), jrs, jvo, j * (GL * 8), 0); }; \
+    auto jld = [&](int j) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(jrs, jvo, j * (GL * 8), 0)); }; \
+    const int n = MF(n);                                                                                             \
+    const bool asv_fixed = (MF(conv) & 4) != 0;                                                                      \
+    double* p_last = reinterpret_cast<double*>(rbase)
+
 // the group integrator kernel: persistent grid, every group takes reactor indices from o.work
 template <int GL, int NM>
 __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL == 16 ? BR_QWPE : BR_QWPE32))) void k_group(
     DevMech M, int N, const double* __restrict__ Tv, const double* __restrict__ Asvv, double* __restrict__ U,
-    const double* __restrict__ tfv, KOpts o, double* __restrict__ stats, double* __restrict__ Jws) {
+    const double* __restrict__ tfv, KOpts o, br_stats* __restrict__ stats, double* __restrict__ Jws) {
     static_assert(NM <= GL, "register tile wider than the group");
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    stage_tables(M, smem_raw);
-    const Tab tb = tab_view<1>(smem_raw, M);
-    constexpr int GPW = 64 / GL;                                        // groups per wave
-    const int lane = threadIdx.x & 63, gl = lane & (GL - 1);
-    const int grp = (int)(threadIdx.x / GL);                            // group within the workgroup
-    const int slot = blockIdx.x * (BR_QWPB * GPW) + grp;                // workspace slot of this group
-    const int RB = grp::block_bytes(GL, NM, MF(nrg), MF(nfo), MF(nrs));
-    char* rbase = smem_raw + M.img_bytes + (size_t)grp * RB;
+    GRP_CONTEXT(M, Jws);
     LCtl* C = (LCtl*)rbase;
     VA<1, GL, grp::vstride(GL, NM)> V{(LDbl*)(rbase + CTL_BYTES), gl};
-    double* sp = reinterpret_cast<double*>(rbase + grp::sp_off(GL, NM));
-    double* fod = reinterpret_cast<double*>(rbase + grp::fod_off(GL, NM, MF(nrg), MF(nrs)));
-    double* skd = fod + 4 * MF(nfo);
-    const int SD = grp::slot_doubles(GL, MF(nrg));                      // global doubles per group slot
-    QKd* kd = launder(Jws) + (size_t)slot * SD + GL * GL;
-    // the group's saved-J slot through a buffer resource: lane offset in a VGPR, the column offset
-    // j GL 8 as the instruction's scalar offset (as 64-bit addresses, the columns past 4 KB of a 32-lane
-    // slot were materialised per column, hoisted out of the loop and spilled)
-    const __amdgpu_buffer_rsrc_t jrs = __builtin_amdgcn_make_buffer_rsrc((void*)launder(Jws), (short)0, 0x7fffffff, 0x00020000);
-    const unsigned jvo = (unsigned)(slot * SD + gl) * 8u;
-    auto jst = [&](int j, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), jrs, jvo, j * (GL * 8), 0); };
-    auto jld = [&](int j) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(jrs, jvo, j * (GL * 8), 0)); };
-    const int n = MF(n);
-    const bool asv_fixed = (MF(conv) & 4) != 0;
-    double* p_last = reinterpret_cast<double*>(rbase);                  // Ctl::p_last is the first field
     // this group's reactor: the first one from the work counter
     auto take = [&]() -> int {
         int v = 0;
@@ -612,24 +620,14 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
 #pragma unroll
     for (int j = 0; j < NM; ++j) a[j] = 0.0;
     unsigned long long cyc0 = 0;
-#if BR_PHASE_CLOCKS   // diagnostic build: this group's shader clocks per phase (br_stats cyc_*)
-    unsigned long long q_rhs_c = 0, q_jac_c = 0, q_lu_c = 0, q_sol_c = 0, q_ctl_c = 0, q_all = 0;
-#define QCLK(v) const unsigned long long v = clock64()
-#define QACC(acc, v) acc += clock64() - v
-#else
-#define QCLK(v)
-#define QACC(acc, v)
-#endif
+    BR_CLK_VARS;
     for (;;) {
         if (__ballot(rid < N) == 0) break;
         if (rid < N) {
             if (fresh) {                                                // ---- CVodeInit for reactor rid
                 fresh = false;
                 cyc0 = wall_clock64();
-#if BR_PHASE_CLOCKS
-                q_rhs_c = q_jac_c = q_lu_c = q_sol_c = q_ctl_c = 0;
-                q_all = clock64();
-#endif
+                BR_CLK_START();
                 T = Tv[rid];
                 Asv = Asvv ? Asvv[rid] : 1.0;
                 Asv_th = asv_fixed ? 1.0 : Asv;
@@ -687,14 +685,14 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 dq_incs<1, GL>(C, V, gl, inc);
                 if (gl == dqj) yv += inc[0];
             }
-            QCLK(c_r);
+            BR_CLK(c_r);
             const double fv = g_rhs<GL>(tb, sp, kd, fod, skd, T, Asv, Asv_th, yv, gl, p_last);
             BR_XG_AFTER_RHS();
-            QACC(q_rhs_c, c_r);
+            BR_ACC(cyc_rhs, c_r);
             double f[1] = {fv}, b[1];
             int act_code;
             bool jac_ready = false;
-            QCLK(c_c);
+            BR_CLK(c_c);
             if (dqj >= 0) {
                 double inc[1];
                 dq_incs<1, GL>(C, V, gl, inc);
@@ -720,69 +718,62 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                     act_code = A_RHS;
                 }
             }
-            QACC(q_ctl_c, c_c);
+            BR_ACC(cyc_ctl, c_c);
             int lu_fail = 0;
             if (act_code == A_SETUP) {
 #if BR_GPRIO   // a wave with a group in its setup (the others idle) issues first
                 __builtin_amdgcn_s_setprio(BR_GPRIO);
 #endif
                 if (!jac_ready && C->newj) {                            // analytic Jacobian at y, saved
-                    QCLK(c_j);
+                    BR_CLK(c_j);
                     g_jac_cols<GL>(tb, sp, kd, fod, skd, T, Asv, Asv_th, gl, jst);   // column passes
 #pragma unroll 1
                     for (int j = n; j < NM; ++j) jst(j, 0.0);                 // padding columns
                     BR_XG_AFTER_JAC();
-                    QACC(q_jac_c, c_j);
+                    BR_ACC(cyc_jac, c_j);
                 }
-                QCLK(c_l);
+                BR_CLK(c_l);
                 double jr[NM];
 #pragma unroll
                 for (int j = 0; j < NM; ++j) jr[j] = jld(j);
                 lu_fail = g_lu<GL, NM>(jr, C->gamma, n, gl, a, orig, dinv);
                 BR_XG_AFTER_LU();
-                QACC(q_lu_c, c_l);
+                BR_ACC(cyc_lu, c_l);
 #if BR_GPRIO
                 __builtin_amdgcn_s_setprio(0);
 #endif
             }
             if (act_code == A_SOLVE || act_code == A_SETUP) {
-                QCLK(c_s);
+                BR_CLK(c_s);
                 double delta[1] = {0.0};
                 if (!lu_fail) {
                     delta[0] = g_solve<GL, NM>(a, orig, dinv, n, gl, b[0]);
                     BR_XG_AFTER_SOLVE();
                 }
-                QACC(q_sol_c, c_s);
-                QCLK(c_p);
+                BR_ACC(cyc_sol, c_s);
+                BR_CLK(c_p);
                 BR_SUB_T(ps_all);
                 act_code = g_post_solve<GL>(C, V, gl, delta, lu_fail);
                 BR_SUB_ADD(13, ps_all);
-                QACC(q_ctl_c, c_p);
+                BR_ACC(cyc_ctl, c_p);
             }
             if (act_code == A_DONE) {                                   // ---- results, next reactor
                 const int status = C->status;
                 const double u_out = status ? V.at(0, 0) : V.at(V_Y, 0);
                 if (gl < n) U[(size_t)rid * n + gl] = u_out;
                 if (stats && gl == 0) {
-                    double* st = stats + (size_t)rid * BR_NSTAT;
-                    st[0] = C->nst; st[1] = C->nfe; st[2] = C->nje; st[3] = C->nsetups; st[4] = C->nni;
-                    st[5] = C->ncfn; st[6] = C->netf; st[7] = (double)status;
-                    st[8] = (double)(wall_clock64() - cyc0);
-#if BR_PHASE_CLOCKS
-                    st[9] = (double)q_rhs_c; st[10] = (double)q_jac_c; st[11] = (double)q_lu_c; st[12] = (double)q_sol_c;
-                    st[14] = (double)q_ctl_c; st[15] = (double)(clock64() - q_all);
-#else
-                    st[9] = st[10] = st[11] = st[12] = st[14] = st[15] = 0.0;
-#endif
-                    st[13] = C->tn;
-                    st[16] = o.ign >= 0 ? (double)C->t_ign : NAN; st[17] = o.ign >= 0 ? (double)C->ign_rate : NAN;
-                    st[18] = o.ign >= 0 ? (double)C->ign_dt : NAN; st[19] = C->nfe_dq;
+                    br_stats& s = stats[rid];
+                    s.nsteps = C->nst; s.nfe = C->nfe; s.nje = C->nje; s.nsetups = C->nsetups; s.nni = C->nni;
+                    s.ncfn = C->ncfn; s.netf = C->netf; s.status = (double)status;
+                    s.cyc_total = (double)(wall_clock64() - cyc0);
+                    BR_CLK_STORE(s);
+                    s.t_end = C->tn;
+                    s.t_ign = o.ign >= 0 ? (double)C->t_ign : NAN; s.ign_rate = o.ign >= 0 ? (double)C->ign_rate : NAN;
+                    s.ign_dt = o.ign >= 0 ? (double)C->ign_dt : NAN; s.nfe_dq = C->nfe_dq;
                 }
                 rid = take();
                 fresh = true;
             }
         }
     }
-#undef QCLK
-#undef QACC
 }

@@ -105,17 +105,6 @@ struct ZH {
     }
 };
 
-#if BR_ASM_MARKS   // analysis builds: phase markers in the ISA listing
-#define LCLK(v) asm volatile("; BR_PHASE_BEGIN " #v)
-#define LACC(acc, v) asm volatile("; BR_PHASE_END " #acc)
-#elif BR_PHASE_CLOCKS
-#define LCLK(v) const unsigned long long v = clock64()
-#define LACC(acc, v) acc += clock64() - v
-#else
-#define LCLK(v)
-#define LACC(acc, v)
-#endif
-
 enum { PH_JAC = 4 };
 enum { A_NONE = 7 };
 constexpr int ST_DEFER = 1;   // lane status: hand the reactor to the wavefront pass
@@ -1081,12 +1070,31 @@ __device__ __forceinline__ void lane_jac(const LaneLay& LL, const double* Lp, co
     }
 }
 
+// br_stats of a lane's reactor, every column in this one place. done: the whole record. Else the hand-over
+// to the wavefront pass: the counters and the ignition marker so far; k_integrate continues from them and
+// writes the rest.
+__device__ __forceinline__ void l_store_stats(br_stats& s, const LCV& c, const KOpts& o, int n, bool done,
+                                              unsigned long long cyc0, PhaseClk clk) {
+    s.nsteps = (double)c.nst; s.nfe = (double)c.nfe; s.nje = (double)c.nje; s.nsetups = (double)c.nsetups;
+    s.nni = (double)c.nni; s.ncfn = (double)c.ncfn; s.netf = (double)c.netf;
+    if (done) {
+        s.status = (double)c.status;
+        s.cyc_total = (double)(wall_clock64() - cyc0);
+        clk.store(s);   // (cyc_jac holds the refill clocks: this engine builds its Jacobian inside its controller)
+        s.t_end = c.tn;
+    }
+    // (the hand-over's marker as it stands: k_integrate reads it back only when it is tracked)
+    const bool ign = !done || o.ign >= 0;
+    s.t_ign = ign ? c.t_ign : NAN; s.ign_rate = ign ? c.ign_rate : NAN; s.ign_dt = ign ? c.ign_dt : NAN;
+    s.nfe_dq = o.dq_jac ? (double)c.nje * n : 0.0;   // (n RHS per DQ Jacobian)
+}
+
 // ------------------------------------------------------------------------------------
 // the lane integrator kernel (persistent grid; 64-thread workgroups, one wave each)
 // ------------------------------------------------------------------------------------
 template <int NM>
 __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __restrict__ Tv, double* __restrict__ U,
-                                             const double* __restrict__ tfv, KOpts o, double* __restrict__ stats,
+                                             const double* __restrict__ tfv, KOpts o, br_stats* __restrict__ stats,
                                              double* __restrict__ Jg, int* __restrict__ queue, double* __restrict__ defer_t0,
                                              int defer_cap) {
     // queue[0]: next reactor; queue[1]: deferred count; queue[2 ..]: deferred reactor ids;
@@ -1112,19 +1120,15 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
     int rid = 0;
     bool has = false, drained = false;
     unsigned long long cyc0 = 0;
-#if BR_PHASE_CLOCKS
-    unsigned long long k_rhs = 0, k_ref = 0, k_lu = 0, k_sol = 0, k_ctl = 0, k_all = 0;
-#endif
+    BR_CLK_VARS;
     for (;;) {
-        LCLK(t0);
+        BR_CLK(t0);
         if (!has && !drained) {                              // take the next reactor
             rid = atomicAdd(queue, 1);
             if (rid < N) {
                 has = true;
                 cyc0 = wall_clock64();
-#if BR_PHASE_CLOCKS
-                k_rhs = k_ref = k_lu = k_sol = k_ctl = 0; k_all = clock64();
-#endif
+                BR_CLK_START();
                 lane_tconst(LL, Lp, G, Tv[rid], n);
                 double su = 0.0;
 #pragma unroll
@@ -1164,19 +1168,19 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
             }
         }
         if (!__any(has)) break;                              // uniform: the whole wave leaves together
-        LACC(k_ref, t0);
-        LCLK(t1);
+        BR_ACC(cyc_jac, t0);   // the refill (taking and initialising reactors) counts as this engine's cyc_jac
+        BR_CLK(t1);
         double f[NM];
         lane_rhs<NM>(LL, Lp, G, y, n, f);
-        LACC(k_rhs, t1);
-        LCLK(t2);
+        BR_ACC(cyc_rhs, t1);
+        BR_CLK(t2);
         double b[NM];
 #pragma unroll
         for (int i = 0; i < NM; ++i) b[i] = 0.0;
         int act = A_NONE;
         if (has) act = l_post_rhs<NM>(c, z, acor, ewt, y, f, b, Lp, LL, G, o, n);
-        LACC(k_ctl, t2);
-        LCLK(t3);
+        BR_ACC(cyc_ctl, t2);
+        BR_CLK(t3);
         int lu_fail = 0;
         if (__any(act == A_SETUP)) {
             if (act == A_SETUP) {                            // A = I - gamma J from the saved J
@@ -1200,17 +1204,17 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
                 }
             }
         }
-        LACC(k_lu, t3);
-        LCLK(t4);
+        BR_ACC(cyc_lu, t3);
+        BR_CLK(t4);
         const bool solve = (act == A_SOLVE) || (act == A_SETUP && !lu_fail);
         if (__any(solve)) {
             if (solve) l_getrs<NM>(G, LL, pv, b);
         }
-        LACC(k_sol, t4);
-        LCLK(t5);
+        BR_ACC(cyc_sol, t4);
+        BR_CLK(t5);
         if (act == A_SOLVE || act == A_SETUP) act = l_post_solve<NM>(c, z, acor, ewt, y, b, lu_fail, o, n);
         if (act == A_RHS && c.pend != PEND_NONE) l_run_pending<NM>(c, z, acor, ewt, y, o, n);
-        LACC(k_ctl, t5);
+        BR_ACC(cyc_ctl, t5);
         if (act == A_DONE && c.status == ST_DEFER) {
             const int di = atomicAdd(queue + 1, 1);
             if (di < defer_cap) {                            // hand over the last accepted state
@@ -1218,13 +1222,7 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
                 defer_t0[di] = c.tn;
 #pragma unroll
                 for (int i = 0; i < NM; ++i) if (i < n) U[(size_t)rid * n + i] = z.z0[i];
-                if (stats) {                                 // counters so far (the wave pass adds its own)
-                    double* st = stats + (size_t)rid * BR_NSTAT;
-                    st[0] = (double)c.nst; st[1] = (double)c.nfe; st[2] = (double)c.nje; st[3] = (double)c.nsetups;
-                    st[4] = (double)c.nni; st[5] = (double)c.ncfn; st[6] = (double)c.netf;
-                    st[16] = c.t_ign; st[17] = c.ign_rate; st[18] = c.ign_dt;
-                    st[19] = o.dq_jac ? (double)c.nje * n : 0.0;   // nfe_dq
-                }
+                if (stats) l_store_stats(stats[rid], c, o, n, false, cyc0, BR_CLK_VALUES);
                 has = false;
             } else {                                         // no room: keep integrating here
                 c.status = 0;
@@ -1238,21 +1236,7 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
 #pragma unroll
             for (int i = 0; i < NM; ++i)
                 if (i < n) U[(size_t)rid * n + i] = status ? z.z0[i] : y[i];
-            if (stats) {
-                double* st = stats + (size_t)rid * BR_NSTAT;
-                st[0] = (double)c.nst; st[1] = (double)c.nfe; st[2] = (double)c.nje; st[3] = (double)c.nsetups;
-                st[4] = (double)c.nni; st[5] = (double)c.ncfn; st[6] = (double)c.netf; st[7] = (double)status;
-                st[8] = (double)(wall_clock64() - cyc0);
-#if BR_PHASE_CLOCKS
-                st[9] = (double)k_rhs; st[10] = (double)k_ref; st[11] = (double)k_lu; st[12] = (double)k_sol;
-                st[14] = (double)k_ctl; st[15] = (double)(clock64() - k_all);
-#else
-                st[9] = st[10] = st[11] = st[12] = st[14] = st[15] = 0.0;
-#endif
-                st[13] = c.tn;
-                st[16] = o.ign >= 0 ? c.t_ign : NAN; st[17] = o.ign >= 0 ? c.ign_rate : NAN;
-                st[18] = o.ign >= 0 ? c.ign_dt : NAN; st[19] = o.dq_jac ? (double)c.nje * n : 0.0;   // nfe_dq
-            }
+            if (stats) l_store_stats(stats[rid], c, o, n, true, cyc0, BR_CLK_VALUES);
             has = false;
         }
     }

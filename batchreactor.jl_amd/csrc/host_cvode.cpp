@@ -505,12 +505,13 @@ extern "C" int br_integrate_host(int n, br_rhs_fn f, void* user, double* u, doub
     }
     if (status) std::copy(cv.zn[0].begin(), cv.zn[0].end(), u);
     if (stats) {
-        std::fill(stats, stats + BR_NSTAT, 0.0);
-        stats[0] = (double)cv.nst; stats[1] = (double)cv.nfe; stats[2] = (double)cv.nje; stats[3] = (double)cv.nsetups;
-        stats[4] = (double)cv.nni; stats[5] = (double)cv.ncfn; stats[6] = (double)cv.netf; stats[7] = (double)status;
-        stats[13] = status ? cv.tn : tf;
-        stats[16] = stats[17] = stats[18] = NAN;
-        stats[19] = (double)cv.nfe_dq;
+        br_stats s{};   // (no device clocks)
+        s.nsteps = (double)cv.nst; s.nfe = (double)cv.nfe; s.nje = (double)cv.nje; s.nsetups = (double)cv.nsetups;
+        s.nni = (double)cv.nni; s.ncfn = (double)cv.ncfn; s.netf = (double)cv.netf; s.status = (double)status;
+        s.t_end = status ? cv.tn : tf;
+        s.t_ign = s.ign_rate = s.ign_dt = NAN;
+        s.nfe_dq = (double)cv.nfe_dq;
+        std::memcpy(stats, &s, sizeof s);
     }
     return status;
 }

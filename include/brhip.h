@@ -136,6 +136,9 @@ typedef struct br_stats {     /* per reactor; counters as CVODE's, then device c
     double ign_dt;            /* width of that step (the resolution of t_ign) [s]            */
     double nfe_dq;            /* RHS evaluations of the DQ Jacobian (CVODE's nfeDQ; not in nfe) */
 } br_stats;
+#ifdef __cplusplus   /* stats arrays are [N][BR_NSTAT] doubles: one br_stats per reactor, no padding */
+static_assert(sizeof(br_stats) == BR_NSTAT * sizeof(double), "br_stats is BR_NSTAT doubles");
+#endif
 
 int         br_version(void);
 const char* br_last_error(void);
