@@ -29,7 +29,8 @@ class Opts(C.Structure):
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_steps", C.c_int), ("device", C.c_int),
                 ("hmax", C.c_double), ("trace_cap", C.c_int), ("unstable_factor", C.c_double),
                 ("ignition_species", C.c_int), ("nout", C.c_int), ("tout", dp), ("yout", dp),
-                ("dq_jacobian", C.c_int), ("tout_per_reactor", C.c_int)]
+                ("dq_jacobian", C.c_int), ("nmult", C.c_int), ("rate_mult", dp), ("rate_mult_row", ip),
+                ("tout_per_reactor", C.c_int)]
 
 
 NSTAT = 20
@@ -50,7 +51,7 @@ EXPORTS = ["br_version", "br_last_error", "br_device_count", "br_mech_create", "
            "br_last_kernel_ms", "br_debug_lu_solve", "br_mech_parse", "br_host_mech_desc", "br_host_mech_sizes",
            "br_host_mech_species", "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml",
            "br_integrate_host", "br_phase_tout_dev", "br_integrate_phase", "br_debug_group_eval",
-           "br_debug_group_lu_solve"]
+           "br_debug_group_lu_solve", "br_sensitivity"]
 
 # br_integrate_host callbacks: int f(void* user, double t, const double* u, double* du);
 # void cb(void* user, double t, const double* u)
@@ -86,6 +87,8 @@ def lib():
     L.br_integrate_multi.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(Opts), dp]
     L.br_phase_tout_dev.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.br_integrate_phase.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.POINTER(Opts), dp, C.c_int, dp, dp, dp]
+    L.br_sensitivity.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.POINTER(Opts), C.c_double, C.c_int, ip, dp, dp, dp, dp,
+                                 C.POINTER(C.c_longlong)]
     L.br_last_kernel_ms.argtypes = [vp, dp]
     L.br_debug_lu_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, ip]
     L.br_debug_lu_solve.restype = C.c_int
@@ -108,7 +111,7 @@ def lib():
               "br_integrate", "br_integrate_traced", "br_integrate_multi", "br_integrate_dev", "br_last_kernel_ms",
               "br_mech_parse", "br_host_mech_desc", "br_host_mech_sizes", "br_host_mech_species",
               "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml", "br_integrate_host",
-              "br_phase_tout_dev", "br_integrate_phase"):
+              "br_phase_tout_dev", "br_integrate_phase", "br_sensitivity"):
         getattr(L, f).restype = C.c_int
     _lib = L
     return L

@@ -299,9 +299,54 @@ __device__ __forceinline__ void stage_tables(const DevMech& M, char* dst) {
     __syncthreads();
 }
 
-// T-only constants (src/BatchReactor.jl:14-17: T is a per-reactor constant); g/RT scratch in accw
-template <int CPL>
-__device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, const RView& R, double T, int lane) {
+// Per-reactor rate multipliers (br_opts.rate_mult): m = mult[row(rid)][reaction], applied to the T-only
+// constants of the three engines' init functions and nowhere else. A launch with multipliers sets bit 0
+// of DevMech::g_par (the table is 8-byte aligned); the MultBlock then sits in the 32 bytes in front of
+// the table. No kernel argument, DevMech field or KOpts field of its own: any of them moves the kernel
+// arguments, which has changed the register allocation of kernels that never read the new one
+// (brhip_ctl.hpp, tout_tag). The table is in the caller's reaction order: gas reactions as in
+// br_mech_desc, then surface reactions. `perm` maps a packed gas position (mech_pack's evaluation order:
+// falloff, +M, elementary) to the caller's index; this is the one place the two orders meet.
+struct MultBlock {
+    const double* mult;   // [nmult][nr] (per launch)
+    const int* row;       // [N] row of each reactor, or nullptr: row = reactor index (per launch)
+    const int* perm;      // [nrg] packed gas position -> gas reaction of br_mech_desc (per mechanism)
+    int nr, pad;          // nrg + nrs
+};
+static_assert(sizeof(MultBlock) == 32, "MultBlock is the 32-byte header of the g_par table");
+constexpr int MULT_HDR_DOUBLES = sizeof(MultBlock) / sizeof(double);
+__device__ __forceinline__ const double* gpar_table() {
+    return reinterpret_cast<const double*>(reinterpret_cast<size_t>(MF(g_par)) & ~(size_t)1);
+}
+struct MultRow {
+    const BR_GLOBAL double* m;     // the reactor's row (nullptr: no multipliers in this launch)
+    const BR_GLOBAL int* perm;
+    int nrg;
+    __device__ __forceinline__ bool on() const { return m != nullptr; }
+    __device__ __forceinline__ double gas(int packed_r) const { return m[perm[packed_r]]; }
+    __device__ __forceinline__ double surf(int r) const { return m[nrg + r]; }
+};
+__device__ __forceinline__ MultRow mult_row(int rid) {
+    const size_t gb = reinterpret_cast<size_t>(MF(g_par));
+    MultRow r{nullptr, nullptr, 0};
+    if (gb & 1) {
+        const BR_GLOBAL MultBlock* b = reinterpret_cast<const BR_GLOBAL MultBlock*>(gb & ~(size_t)1) - 1;
+        const BR_GLOBAL int* rows = (const BR_GLOBAL int*)b->row;
+        const size_t row = rows ? (size_t)rows[rid] : (size_t)rid;
+        r.m = (const BR_GLOBAL double*)b->mult + row * (size_t)b->nr;
+        r.perm = (const BR_GLOBAL int*)b->perm;
+        r.nrg = MF(nrg);
+    }
+    return r;
+}
+
+// T-only constants (src/BatchReactor.jl:14-17: T is a per-reactor constant); g/RT scratch in accw.
+// rid: the reactor's index in the launch (its row of rate multipliers). MULT = false: the parity kernels
+// (k_rates, k_rhs, k_jac), whose entry points take no br_opts and never see a tagged g_par
+template <int CPL, bool MULT = false>
+__device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, const RView& R, double T, int lane,
+                                            int rid = 0) {
+    const MultRow mr = MULT ? mult_row(rid) : MultRow{nullptr, nullptr, 0};
     const double lT = log(T);
     double* grt = R.sp + Lay<CPL>::ACCW;
     if (lane == 0) R.sp[Lay<CPL>::ONE] = 1.0;
@@ -319,8 +364,9 @@ __device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, con
     for (int r = lane; r < MF(nrg); r += WAVE) {
         const auto rec = rx_rec(tb.rx, r);
         const uint32_t info = rec[2];
-        const double* gp = MF(g_par) + 4 * r;
-        const double kf = gp[0] * exp(gp[1] * lT - gp[2] / T);
+        const double* gp = (MULT ? gpar_table() : MF(g_par)) + 4 * r;
+        const double kf1 = gp[0] * exp(gp[1] * lT - gp[2] / T);
+        const double kf = (MULT && mr.on()) ? kf1 * mr.gas(r) : kf1;   // (kr = kf / Kc: both directions scale)
         double kr = 0.0;
         if (gi_rev(info)) {
             double dg = 0.0;
@@ -337,7 +383,7 @@ __device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, con
             const int fi = gi_foidx(info);
             const double* fp = MF(fo_par) + 8 * fi;
             double* fo = R.fod + 4 * fi;
-            fo[0] = fp[0] * exp(fp[1] * lT - fp[2] / T) / kf;   // k0 / k_inf
+            fo[0] = fp[0] * exp(fp[1] * lT - fp[2] / T) / kf1;   // k0 / k_inf (of the unscaled pair)
             double fcv = 1.0;
             if (gi_troe(info)) {
                 fcv = (1 - fp[3]) * exp(-T / fp[4]) + fp[3] * exp(-T / fp[5]);
@@ -356,6 +402,7 @@ __device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, con
         double k;
         if (si_stick(info)) k = sp[0] * sqrt(RT / (2 * M_PI * sp[3]));
         else k = sp[0] * pow(T, sp[1]) * exp(-sp[2] / RT);
+        if (MULT && mr.on()) k *= mr.surf(r);
         R.skd[2 * r] = k;
     }
     // the RXD stores reach L2 and this CU's L1 is invalidated before any lane reads the slot

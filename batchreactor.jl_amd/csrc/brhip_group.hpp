@@ -112,8 +112,9 @@ __device__ __forceinline__ double group_bcast(double v) {
 // species in the ACCW slots (scratch)
 template <int GL>
 __device__ __forceinline__ void g_init_tconst(const Tab& tb, double* sp, QKd* kd, double* fod, double* skd, double T,
-                                              int gl) {
+                                              int gl, int rid = 0) {
     typedef grp::GLay<GL> L;
+    const MultRow mr = mult_row(rid);   // the reactor's rate multipliers (br_opts.rate_mult), as init_tconst
     const double lT = log(T);
     double* grt = sp + L::ACCW;
     const int ng = MF(ng), nrg = MF(nrg), nrs = MF(nrs);
@@ -131,8 +132,9 @@ __device__ __forceinline__ void g_init_tconst(const Tab& tb, double* sp, QKd* kd
     for (int r = gl; r < nrg; r += GL) {
         const auto rec = rx_rec(tb.rx, r);
         const uint32_t info = rec[2];
-        const double* gp = MF(g_par) + 4 * r;
-        const double kf = gp[0] * exp(gp[1] * lT - gp[2] / T);
+        const double* gp = gpar_table() + 4 * r;
+        const double kf1 = gp[0] * exp(gp[1] * lT - gp[2] / T);
+        const double kf = mr.on() ? kf1 * mr.gas(r) : kf1;
         double kr = 0.0;
         if (gi_rev(info)) {
             double dg = 0.0;
@@ -149,7 +151,7 @@ __device__ __forceinline__ void g_init_tconst(const Tab& tb, double* sp, QKd* kd
             const int fi = gi_foidx(info);
             const double* fp = MF(fo_par) + 8 * fi;
             double* fo = fod + 4 * fi;
-            fo[0] = fp[0] * exp(fp[1] * lT - fp[2] / T) / kf;
+            fo[0] = fp[0] * exp(fp[1] * lT - fp[2] / T) / kf1;
             double fcv = 1.0;
             if (gi_troe(info)) {
                 fcv = (1 - fp[3]) * exp(-T / fp[4]) + fp[3] * exp(-T / fp[5]);
@@ -168,6 +170,7 @@ __device__ __forceinline__ void g_init_tconst(const Tab& tb, double* sp, QKd* kd
         double k;
         if (si_stick(info)) k = spr[0] * sqrt(RT / (2 * M_PI * spr[3]));
         else k = spr[0] * pow(T, spr[1]) * exp(-spr[2] / RT);
+        if (mr.on()) k *= mr.surf(r);
         skd[r] = k;
     }
     // the kd stores reach L2 and this CU's L1 is invalidated before any lane reads the slot (it held
@@ -634,7 +637,7 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 C->a_rtol = o.rtol; C->a_atol = o.atol; C->a_hmax_inv = o.hmax_inv; C->a_ufac = o.ufac;
                 C->a_max_steps = o.max_steps; C->a_trace_cap = 0; C->a_trace = nullptr; C->a_rid = rid; C->a_n = n;
                 C->a_ign = o.ign; C->a_nout = o.nout; C->a_tout = o.tout; C->a_yout = o.yout;
-                g_init_tconst<GL>(tb, sp, kd, fod, skd, T, gl);
+                g_init_tconst<GL>(tb, sp, kd, fod, skd, T, gl, rid);
                 const bool act = gl < n;
                 const double u0 = act ? U[(size_t)rid * n + gl] : 0.0;
 #pragma unroll

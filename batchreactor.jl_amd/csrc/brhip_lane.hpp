@@ -846,7 +846,8 @@ __device__ __forceinline__ int lane_sp(uint32_t w, int e, int n) {   // record s
     const int k = (int)((w >> (8 * e)) & 255);
     return k == Lay<1>::ONE ? n : k;
 }
-__device__ __forceinline__ void lane_tconst(const LaneLay& LL, double* Lp, const GRows& G, double T, int n) {
+__device__ __forceinline__ void lane_tconst(const LaneLay& LL, double* Lp, const GRows& G, double T, int n, int rid) {
+    const MultRow mr = mult_row(rid);   // this lane's reactor's rate multipliers (br_opts.rate_mult), as init_tconst
     const double lT = log(T);
     const int ng = MF(ng), nrg = MF(nrg);
     for (int k = 0; k < ng; ++k) {                   // g/RT (NASA-7) into the acc rows
@@ -862,8 +863,9 @@ __device__ __forceinline__ void lane_tconst(const LaneLay& LL, double* Lp, const
     for (int r = 0; r < nrg; ++r) {
         const auto rq = rx_rec(rx, r);
         const uint32_t w0 = rq[0], w1 = rq[1], info = rq[2];
-        const CF64* gp = (const CF64*)MF(g_par) + 4 * r;
-        const double kf = gp[0] * exp(gp[1] * lT - gp[2] / T);
+        const CF64* gp = (const CF64*)gpar_table() + 4 * r;
+        const double kf1 = gp[0] * exp(gp[1] * lT - gp[2] / T);
+        const double kf = mr.on() ? kf1 * mr.gas(r) : kf1;
         double kr = 0.0;
         if (gi_rev(info)) {
             double dg = 0.0;
@@ -879,7 +881,7 @@ __device__ __forceinline__ void lane_tconst(const LaneLay& LL, double* Lp, const
         if (gi_tb(info) == 2) {
             const int fi = gi_foidx(info);
             const CF64* fp = (const CF64*)MF(fo_par) + 8 * fi;
-            G.st(LL.g_fod + 4 * fi, fp[0] * exp(fp[1] * lT - fp[2] / T) / kf);   // k0 / k_inf
+            G.st(LL.g_fod + 4 * fi, fp[0] * exp(fp[1] * lT - fp[2] / T) / kf1);   // k0 / k_inf
             double fcv = 1.0;
             if (gi_troe(info)) {
                 fcv = (1 - fp[3]) * exp(-T / fp[4]) + fp[3] * exp(-T / fp[5]);
@@ -1129,7 +1131,7 @@ __global__ __launch_bounds__(64) void k_lane(DevMech M, int N, const double* __r
                 has = true;
                 cyc0 = wall_clock64();
                 BR_CLK_START();
-                lane_tconst(LL, Lp, G, Tv[rid], n);
+                lane_tconst(LL, Lp, G, Tv[rid], n, rid);
                 double su = 0.0;
 #pragma unroll
                 for (int i = 0; i < NM; ++i) {

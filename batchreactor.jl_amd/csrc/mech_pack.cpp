@@ -93,6 +93,7 @@ int mech_pack(const br_mech_desc* d, const PackOpts& opts, PackedMech* out, std:
     std::vector<int> perm;
     for (int pass = 2; pass >= 0; --pass)
         for (int r = 0; r < nrg; ++r) if (d->g_tb[r] == pass) perm.push_back(r);
+    out->g_perm = perm;
     int ntb = 0, nfo = 0;
     for (int i = 0; i < nrg; ++i) {
         if (d->g_tb[perm[i]] == 2) nfo++;

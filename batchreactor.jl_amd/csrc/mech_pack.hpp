@@ -20,6 +20,8 @@ struct PackedMech {
     std::vector<uint4> img;    // LDS table image, dm.img_bytes
     std::vector<double> nasa, g_par, fo_par, s_par, tb_eff;
     std::vector<int> g_dnu, col_ptr, col_rx;
+    std::vector<int> g_perm;   // [nrg] gas reaction of br_mech_desc at each packed (evaluation-order) position:
+                               // a per-reaction array in the caller's order (br_opts.rate_mult) is read through it
 };
 
 // d: sizes checked by the caller (ng > 0, the others >= 0, ng + ns <= 72).

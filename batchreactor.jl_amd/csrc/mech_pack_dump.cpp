@@ -56,7 +56,8 @@ int main(int argc, char** argv) {
     }
     bool ok = write_bin(dir, "img", p.img) & write_bin(dir, "nasa", p.nasa) & write_bin(dir, "g_par", p.g_par) &
               write_bin(dir, "g_dnu", p.g_dnu) & write_bin(dir, "fo_par", p.fo_par) & write_bin(dir, "s_par", p.s_par) &
-              write_bin(dir, "tb_eff", p.tb_eff) & write_bin(dir, "col_ptr", p.col_ptr) & write_bin(dir, "col_rx", p.col_rx);
+              write_bin(dir, "tb_eff", p.tb_eff) & write_bin(dir, "col_ptr", p.col_ptr) & write_bin(dir, "col_rx", p.col_rx) &
+              write_bin(dir, "g_perm", p.g_perm);
     FILE* f = fopen((dir + "/devmech.txt").c_str(), "w");
     if (!f) return 1;
     const brhip::DevMech& M = p.dm;

@@ -51,6 +51,29 @@ def phase_grid(t_ign, tau, tf):
         return np.where(p <= tf[:, None], p, np.nan)
 
 
+def rate_mult_table(rate_mult, rate_mult_row, N, nr):
+    """The rate_mult / rate_mult_row arguments of the integrate calls as C arrays (br_opts.rate_mult):
+    rate_mult [nmult, nr] float64 with nr = nrg + nrs (gas reactions in mechanism order, then surface
+    reactions), rate_mult_row [N] int32 giving each reactor's row, or None: then the table is dense,
+    nmult == N. Returns (table or None, rows or None). Shapes are checked here (ValueError, before the
+    library is called); the values -- finite, >= 0, rows in range -- by the library."""
+    if rate_mult is None:
+        if rate_mult_row is not None:
+            raise ValueError("rate_mult_row without rate_mult")
+        return None, None
+    m = np.ascontiguousarray(rate_mult, dtype=np.float64)
+    if m.ndim != 2 or m.shape[1] != nr or m.shape[0] < 1:
+        raise ValueError(f"rate_mult must be [nmult, {nr}] (gas reactions, then surface reactions), got shape {m.shape}")
+    if rate_mult_row is None:
+        if m.shape[0] != N:
+            raise ValueError(f"rate_mult has {m.shape[0]} rows for N = {N} reactors: pass rate_mult_row, or one row per reactor")
+        return m, None
+    rows = np.asarray(rate_mult_row)
+    if rows.shape != (N,) or not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError(f"rate_mult_row must be {N} integers, got shape {rows.shape} of {rows.dtype}")
+    return m, np.ascontiguousarray(rows, dtype=np.int32)
+
+
 class Engine:
     def __init__(self, mech: Mechanism, device: int = 0):
         L = _lib.lib()
@@ -81,6 +104,7 @@ class Engine:
         _lib.check(L.br_mech_create(C.byref(desc), device, C.byref(h)))
         self.h = h
         self.n, self.ng, self.ns = mech.n, mech.ng, mech.ns
+        self.nr = mech.nrg + mech.nrs   # row length of a rate-multiplier table
         # 1-based br_opts.ignition_species (0: the mechanism has no OH, t_ign not tracked)
         self.ign1 = mech.gas_species.index(IGNITION_MARKER) + 1 if IGNITION_MARKER in mech.gas_species else 0
         self.nmax = 16 if self.n <= 16 else 32 if self.n <= 32 else 56 if self.n <= 56 else 64 if self.n <= 64 else 72   # kernel tile
@@ -164,14 +188,25 @@ class Engine:
                                                   _lib.dptr(J)))
         return du, J
 
-    def _opts(self, rtol, atol, max_steps, trace_cap=0, unstable_factor=0.0, tout=None, yout=None, dq_jacobian=False):
+    def _mult(self, rate_mult, rate_mult_row, N):
+        """rate_mult_table for this mechanism's nrg + nrs reactions; (None, None) without multipliers"""
+        if rate_mult is None and rate_mult_row is None:
+            return None, None
+        return rate_mult_table(rate_mult, rate_mult_row, N, self.nr)
+
+    def _opts(self, rtol, atol, max_steps, trace_cap=0, unstable_factor=0.0, tout=None, yout=None, dq_jacobian=False,
+              mult=None, mult_row=None):
         nout = 0 if tout is None else tout.shape[-1]   # tout: [nout], or [N, nout] (one row per reactor)
-        return _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout,
-                         _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, int(dq_jacobian),
-                         int(nout > 0 and tout.ndim == 2))
+        o = _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout,
+                      _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, int(dq_jacobian),
+                      tout_per_reactor=int(nout > 0 and tout.ndim == 2))
+        if mult is not None:   # (arrays from rate_mult_table; the caller keeps them alive for the call)
+            o.nmult, o.rate_mult = mult.shape[0], _lib.dptr(mult)
+            o.rate_mult_row = _lib.iptr(mult_row) if mult_row is not None else None
+        return o
 
     def integrate(self, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, trace_cap=0, tout=None,
-                  unstable_factor=0.0, dq_jacobian=False):
+                  unstable_factor=0.0, dq_jacobian=False, rate_mult=None, rate_mult_row=None):
         """Integrate N reactors 0 -> tf. With trace_cap > 0 also returns the per-step rows
         trace[N, trace_cap+1, 2n+4] = (t, h, q, p_last, u[n], y_last[n]): u the accepted state, y_last
         and p_last the state and pressure of the step's last RHS evaluation (save_data semantics).
@@ -179,14 +214,19 @@ class Engine:
         states at those times (CVODE CV_NORMAL output, the step sequence is unchanged). tout is one
         1-D grid for all reactors or a 2-D [N, nout] array, row i reactor i's own grid (NaN = no output,
         trailing padding only; rows of yout without an output stay 0).
-        dq_jacobian: CVODE's difference-quotient Jacobian (the reference's setting), both engines."""
+        dq_jacobian: CVODE's difference-quotient Jacobian (the reference's setting), both engines.
+        rate_mult [nmult, nrg + nrs] scales the net rate of reaction r of reactor i by
+        rate_mult[row(i), r] (gas reactions in mechanism order, then surface reactions; forward and
+        reverse together; 0 switches a reaction off); rate_mult_row [N] gives the rows, None = one row
+        per reactor."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
+        mult, mrow = self._mult(rate_mult, rate_mult_row, N)
         to, _ = output_grid(tout, N)
         T, A, tf = self._arr(T, N), self._arr(Asv, N), self._arr(tf, N)
         st = np.zeros((N, _lib.NSTAT))
         yo = None if to is None else np.zeros((N, to.shape[-1], self.n))
-        o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian)
+        o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian, mult, mrow)
         L = _lib.lib()
         if trace_cap > 0:
             tr = np.zeros((N, trace_cap + 1, 2 * self.n + 4))
@@ -203,11 +243,21 @@ class Engine:
 
     def integrate_device(self, T_ptr, Asv_ptr, u_ptr, tf_ptr, stats_ptr, N, stream_ptr=None, rtol=1e-6,
                          atol=1e-10, max_steps=100000, tout_ptr=None, yout_ptr=None, nout=0, tout_per_reactor=False,
-                         dq_jacobian=False):
+                         dq_jacobian=False, rate_mult=None, rate_mult_row=None, nmult=0):
         """Device-resident variant: raw device pointers (e.g. torch tensor data_ptr()). Dense output
         with tout_ptr / yout_ptr / nout: device arrays tout [nout], or [N, nout] with tout_per_reactor
-        (e.g. what phase_tout_device built), and yout [N, nout, n]."""
+        (e.g. what phase_tout_device built), and yout [N, nout, n]. Rate multipliers: rate_mult is the
+        device pointer of a float64 [nmult, nrg + nrs] table, rate_mult_row that of int32 [N] row indices
+        (None: nmult == N, row i); the library trusts the device arrays."""
         o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        if rate_mult:
+            if nmult < 1 or (not rate_mult_row and nmult != N):
+                raise ValueError(f"rate_mult needs nmult >= 1, and nmult == N = {N} without rate_mult_row; got {nmult}")
+            o.nmult = int(nmult)
+            o.rate_mult = C.cast(C.c_void_p(rate_mult), _lib.dp)
+            o.rate_mult_row = C.cast(C.c_void_p(rate_mult_row), _lib.ip) if rate_mult_row else None
+        elif rate_mult_row:
+            raise ValueError("rate_mult_row without rate_mult")
         if nout and tout_ptr and yout_ptr:
             o.nout, o.tout_per_reactor = int(nout), int(bool(tout_per_reactor))
             o.tout, o.yout = C.cast(C.c_void_p(tout_ptr), _lib.dp), C.cast(C.c_void_p(yout_ptr), _lib.dp)
@@ -215,14 +265,17 @@ class Engine:
                                                C.c_void_p(u_ptr), C.c_void_p(tf_ptr), C.byref(o),
                                                C.c_void_p(stats_ptr), C.c_void_p(stream_ptr or 0)))
 
-    def integrate_phase(self, T, Asv, u0, tf, tau, rtol=1e-6, atol=1e-10, max_steps=100000, dq_jacobian=False):
+    def integrate_phase(self, T, Asv, u0, tf, tau, rtol=1e-6, atol=1e-10, max_steps=100000, dq_jacobian=False,
+                        rate_mult=None, rate_mult_row=None):
         """Ignition-phase sampling (br_integrate_phase): the states at t = tau[j] * t_ign[i], two passes
         on the device from the same u0 (t_ign, then the outputs at the grid br_phase_tout_dev builds).
         Returns (u, stats) as integrate, with stats["tout"] [N, ntau] (phase_grid(t_ign, tau, tf): NaN
         where t_ign is unknown or the phase is past tf) and stats["yout"] [N, ntau, n] (rows of NaN
-        entries stay 0). Needs the ignition marker species in the mechanism."""
+        entries stay 0). Needs the ignition marker species in the mechanism. rate_mult / rate_mult_row as
+        integrate: both passes run with them."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
+        mult, mrow = self._mult(rate_mult, rate_mult_row, N)
         tau = np.ascontiguousarray(np.atleast_1d(tau), dtype=np.float64)
         if tau.ndim != 1 or tau.size == 0:
             raise ValueError(f"tau must be a non-empty 1-D array, got shape {tau.shape}")
@@ -230,13 +283,57 @@ class Engine:
         st = np.zeros((N, _lib.NSTAT))
         to = np.zeros((N, tau.size))
         yo = np.zeros((N, tau.size, self.n))
-        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, mult=mult, mult_row=mrow)
         _lib.check(_lib.lib().br_integrate_phase(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),
                                                  C.byref(o), _lib.dptr(st), tau.size, _lib.dptr(tau), _lib.dptr(to),
                                                  _lib.dptr(yo)))
         stats = {k: st[:, i] for i, k in enumerate(STAT_FIELDS)}
         stats["tout"], stats["yout"] = to, yo
         return u, stats
+
+    def sensitivity(self, T, Asv, u0, tf, factor=2.0, reactions=None, states=False, rtol=1e-6, atol=1e-10,
+                    max_steps=100000, dq_jacobian=False):
+        """Brute-force logarithmic sensitivities to the rate constants (br_sensitivity), built and reduced
+        on the device: every base reactor is integrated with each selected reaction's rate times and
+        over `factor`. reactions: 0-based indices (gas reactions in mechanism order, then surface
+        reactions), None = all. Returns a dict with
+          "S_tign" [N, nsel]: d ln t_ign / d ln k_r (central difference; only with the ignition marker
+                   species in the mechanism),
+          "S_u" [N, nsel, n] (with states=True): d u_k(tf) / d ln k_r,
+          "u" [N, n] and "stats": the unperturbed end states and stats, as integrate's,
+          "nbad": entries set to NaN (a perturbed run failed, or has no t_ign),
+          "reactions": the indices used."""
+        u0 = np.ascontiguousarray(np.atleast_2d(u0), dtype=np.float64)
+        N = u0.shape[0]
+        if not (np.isfinite(factor) and factor > 1.0):
+            raise ValueError(f"factor must be finite and > 1, got {factor}")
+        if reactions is None:
+            rx = np.arange(self.nr, dtype=np.int32)
+        else:
+            rx = np.asarray(reactions)
+            if rx.ndim != 1 or rx.size == 0 or not np.issubdtype(rx.dtype, np.integer):
+                raise ValueError("reactions must be a non-empty 1-D sequence of integers")
+            if rx.min() < 0 or rx.max() >= self.nr:
+                raise ValueError(f"reactions must be in [0, {self.nr}), got {rx.min()} .. {rx.max()}")
+            rx = np.ascontiguousarray(rx, dtype=np.int32)
+        T, A, tf = self._arr(T, N), self._arr(Asv, N), self._arr(tf, N)
+        nsel = rx.size
+        St = np.zeros((N, nsel)) if self.ign1 else None
+        Su = np.zeros((N, nsel, self.n)) if states else None
+        u = np.zeros((N, self.n))
+        st = np.zeros((N, _lib.NSTAT))
+        nbad = C.c_longlong(0)
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        _lib.check(_lib.lib().br_sensitivity(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u0), _lib.dptr(tf),
+                                             C.byref(o), float(factor), nsel, _lib.iptr(rx), _lib.dptr(St),
+                                             _lib.dptr(Su), _lib.dptr(u), _lib.dptr(st), C.byref(nbad)))
+        out = {"u": u, "stats": {k: st[:, i] for i, k in enumerate(STAT_FIELDS)}, "nbad": nbad.value,
+               "reactions": rx}
+        if St is not None:
+            out["S_tign"] = St
+        if Su is not None:
+            out["S_u"] = Su
+        return out
 
     def phase_tout_device(self, stats, tau, tf, out=None, stream_ptr=None):
         """br_phase_tout_dev on torch tensors of this engine's device: stats [N, NSTAT] as
@@ -268,18 +365,21 @@ class Engine:
         return float(ms[0])
 
 
-def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, tout=None):
+def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, tout=None, rate_mult=None,
+                    rate_mult_row=None):
     """br_integrate_multi: the ensemble split into contiguous slices over `engines` (one Engine per
     GPU, same mechanism), integrated concurrently; returns (u, stats) in ensemble order. tout as
-    Engine.integrate: [nout], or [N, nout] for per-reactor grids (sliced with the ensemble)."""
+    Engine.integrate: [nout], or [N, nout] for per-reactor grids (sliced with the ensemble). rate_mult /
+    rate_mult_row as Engine.integrate (the row indices, or the rows of a dense table, are sliced too)."""
     e0 = engines[0]
     u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
     N = u.shape[0]
+    mult, mrow = e0._mult(rate_mult, rate_mult_row, N)
     to, _ = output_grid(tout, N)
     T, A, tf = e0._arr(T, N), e0._arr(Asv, N), e0._arr(tf, N)
     st = np.zeros((N, _lib.NSTAT))
     yo = None if to is None else np.zeros((N, to.shape[-1], e0.n))
-    o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo)
+    o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo, mult=mult, mult_row=mrow)
     L = _lib.lib()
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     _lib.check(L.br_integrate_multi(hs, len(engines), N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),

@@ -111,6 +111,22 @@ typedef struct br_opts {
                                  the reference's CVODE_BDF() setting, src/BatchReactor.jl:140,
                                  :204), n extra RHS per Jacobian, in every engine (lane,
                                  group, wavefront); 0 (default): the analytic Jacobian       */
+    int nmult;                /* rows of rate_mult; 0 = no multipliers (default)            */
+    const double* rate_mult;  /* [nmult][nrg+nrs] per-reactor rate multipliers, mechanism order: gas
+                                 reactions as in br_mech_desc, then surface reactions. The net rate of
+                                 reaction r of reactor i is scaled by m = rate_mult[row(i)][r], applied
+                                 to the T-only constants: gas kf *= m before kr = kf / Kc (both
+                                 directions scale, equilibrium is kept; a falloff's k0 / k_inf is
+                                 untouched, so k_inf and k0 scale together), surface k *= m (sticking
+                                 and Arrhenius forms; the coverage factor stays). m finite and >= 0;
+                                 0 switches the reaction off. Every engine and both Jacobians honour
+                                 it. Host memory for br_integrate, _traced, _multi and _phase (every
+                                 entry and row index checked, BR_ERR_INPUT names the first bad one),
+                                 device memory for br_integrate_dev, which trusts the arrays       */
+    const int* rate_mult_row; /* [N] row of reactor i, or NULL: then nmult == N and row i.
+                                 (These three sit before tout_per_reactor, which stays the last
+                                 field: a caller built against the earlier header must be rebuilt,
+                                 as for any growth of this struct; br_version() tells them apart) */
     int tout_per_reactor;     /* 0 (default): tout is one grid [nout] shared by all reactors.
                                  1: tout is [N][nout], row i the ascending output times of
                                  reactor i (host memory for br_integrate, _traced and _multi,
@@ -260,6 +276,25 @@ int br_phase_tout_dev(int N, br_stats* dstats /*read only*/, int ntau, const dou
 int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                        const br_opts* opts, br_stats* stats, int ntau, const double* tau,
                        double* tout /*[N][ntau] out*/, double* yout /*[N][ntau][n] out*/);
+
+/* brute-force logarithmic sensitivities to the rate constants, built and reduced on the device. With
+ * f = factor > 1 and reaction r = rxn[j] (0-based, mechanism order as br_opts.rate_mult; rxn NULL = all
+ * nrg + nrs reactions, nsel ignored):
+ *   S_tign[i][j]  = (ln t_ign(k_r f) - ln t_ign(k_r / f)) / (2 ln f)   = d ln t_ign / d ln k_r
+ *                   (needs opts->ignition_species, else BR_ERR_INPUT)
+ *   S_u[i][j][k]  = (u_k(tf; k_r f) - u_k(tf; k_r / f)) / (2 ln f)     = d u_k(tf) / d ln k_r
+ * Each base reactor is expanded on the device into 2 nsel + 1 reactors that share one multiplier table
+ * (row 0 unperturbed), integrated with br_integrate_dev in chunks of base reactors sized by a memory
+ * budget (env BRHIP_SENS_CHUNK = base reactors per launch overrides it; the results do not depend on
+ * it), and reduced there: only S, the unperturbed end states u[N][n] and their stats cross to the host.
+ * An entry is NaN when either perturbed run failed, S_tign also when either has no t_ign; *nbad counts
+ * the NaN entries written. opts->rate_mult must be unset; the output fields of opts are ignored. Host
+ * memory throughout; S_tign, S_u, u, stats and nbad may each be NULL. */
+int br_sensitivity(br_mech* m, int N, const double* T, const double* Asv, const double* u0, const double* tf,
+                   const br_opts* opts, double factor, int nsel, const int* rxn /*[nsel] or NULL = all*/,
+                   double* S_tign /*[N][nsel] or NULL*/, double* S_u /*[N][nsel][n] or NULL*/,
+                   double* u /*[N][n] out: unperturbed end states, or NULL*/, br_stats* stats /*[N] unperturbed, or NULL*/,
+                   long long* nbad /*entries set to NaN, or NULL*/);
 
 /* dense-solver check (tests): factor I - gamma_i*J_i with the engine's batched LU and solve
  * x_i = (I - gamma_i J_i)^-1 b_i. J[N][n][n] row-major; fail[i] = 0 or (k+1) for a zero pivot. */

@@ -54,6 +54,9 @@ struct BrOpts
     tout::Ptr{Float64}          # [nout] ascending output times ([nout x N] with tout_per_reactor)
     yout::Ptr{Float64}          # [N][nout][n]
     dq_jacobian::Cint           # 1: CVODE's DQ Jacobian (cvLsDenseDQJac, the reference's setting), every engine
+    nmult::Cint                 # rows of rate_mult; 0 = no multipliers
+    rate_mult::Ptr{Float64}     # [nrg+nrs x nmult]: column q the multipliers of row q, gas reactions in mechanism order, then surface
+    rate_mult_row::Ptr{Cint}    # [N] 0-based row of reactor i, or C_NULL: nmult == N, row i
     tout_per_reactor::Cint      # 1: tout is [nout x N], column i reactor i's own ascending grid (NaN = no output, trailing only)
 end
 # dq_jacobian=true selects CVODE's difference-quotient Jacobian, the reference's CVODE_BDF() setting
@@ -61,7 +64,15 @@ end
 BrOpts(; rtol=1e-6, atol=1e-10, max_steps=100_000, device=0, hmax=0.0, unstable_factor=0.0, ignition_species=0,
        dq_jacobian::Bool=false, tout_per_reactor::Bool=false) =
     BrOpts(rtol, atol, Cint(max_steps), Cint(device), Float64(hmax), Cint(0), Float64(unstable_factor),
-           Cint(ignition_species), Cint(0), C_NULL, C_NULL, Cint(dq_jacobian), Cint(tout_per_reactor))
+           Cint(ignition_species), Cint(0), C_NULL, C_NULL, Cint(dq_jacobian), Cint(0), C_NULL, C_NULL,
+           Cint(tout_per_reactor))
+# the same options with a rate-multiplier table (br_opts.rate_mult): `mult` is (nrg+nrs) x nmult, `rows` the
+# 0-based row of every reactor or nothing (one column per reactor). The caller keeps both arrays alive
+# (GC.@preserve) for the call that takes the options.
+with_rate_mult(o::BrOpts, mult::Matrix{Float64}, rows::Union{Nothing,Vector{Cint}}=nothing) =
+    BrOpts(o.rtol, o.atol, o.max_steps, o.device, o.hmax, o.trace_cap, o.unstable_factor, o.ignition_species,
+           o.nout, o.tout, o.yout, o.dq_jacobian, Cint(size(mult, 2)), pointer(mult),
+           rows === nothing ? Ptr{Cint}(C_NULL) : pointer(rows), o.tout_per_reactor)
 
 # br_stats rows of the [NSTAT x N] matrix returned below
 const STAT_FIELDS = (:nsteps, :nfe, :nje, :nsetups, :nni, :ncfn, :netf, :status, :cyc_total, :cyc_rhs, :cyc_jac,
@@ -98,7 +109,8 @@ function integrate_traced!(m::Ptr{Cvoid}, T, Asv, u::Matrix{Float64}, tf; cap::I
     stats = zeros(NSTAT, N)
     trace = zeros(2n + 4, cap + 1, N)
     o = BrOpts(opts.rtol, opts.atol, opts.max_steps, opts.device, opts.hmax, Cint(cap), opts.unstable_factor,
-               opts.ignition_species, Cint(0), C_NULL, C_NULL, opts.dq_jacobian, Cint(0))
+               opts.ignition_species, Cint(0), C_NULL, C_NULL, opts.dq_jacobian,
+               opts.nmult, opts.rate_mult, opts.rate_mult_row, Cint(0))
     check(ccall((:br_integrate_traced, lib), Cint,
                 (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BrOpts}, Ptr{Float64},
                  Ptr{Float64}), m, N, T, Asv, u, tf, Ref(o), stats, trace))
@@ -135,6 +147,32 @@ phase_tout_dev!(dtout::Ptr{Float64}, N::Integer, dstats::Ptr{Float64}, ntau::Int
     check(ccall((:br_phase_tout_dev, lib), Cint,
                 (Cint, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
                 N, dstats, ntau, dtau, dtf, dtout, stream))
+
+"""Brute-force logarithmic sensitivities to the rate constants (br_sensitivity), built and reduced on
+the device: S_tign[j, i] = d ln t_ign / d ln k_r and (with `states=true`) S_u[k, j, i] = d u_k(tf) / d ln k_r
+for r = rxn[j] (0-based: gas reactions in mechanism order, then surface reactions; `nothing` = all
+nrg + nrs), by central differences with the rate times and over `factor`. `u0` is n x N and is not
+modified. `opts.ignition_species` must be set for S_tign. Returns (S_tign [nsel x N], S_u [n x nsel x N]
+or nothing, u [n x N] unperturbed end states, stats [NSTAT x N], nbad = entries set to NaN).
+(Bound with @ccall: the arguments are those of the prototype in include/brhip.h, in its order.)"""
+function sensitivity(m::Ptr{Cvoid}, T::Vector{Float64}, Asv::Vector{Float64}, u0::Matrix{Float64},
+                     tf::Vector{Float64}, nr::Integer; factor::Real=2.0, rxn::Union{Nothing,Vector{Cint}}=nothing,
+                     states::Bool=false, opts::BrOpts=BrOpts())
+    n, N = size(u0)
+    nsel = rxn === nothing ? Int(nr) : length(rxn)
+    S_t = zeros(nsel, N)
+    S_u = states ? zeros(n, nsel, N) : nothing
+    u = zeros(n, N)
+    stats = zeros(NSTAT, N)
+    nbad = Ref{Clonglong}(0)
+    o = Ref(opts)
+    check(@ccall lib.br_sensitivity(m::Ptr{Cvoid}, N::Cint, T::Ptr{Float64}, Asv::Ptr{Float64}, u0::Ptr{Float64},
+                                    tf::Ptr{Float64}, o::Ref{BrOpts}, Float64(factor)::Cdouble, nsel::Cint,
+                                    (rxn === nothing ? C_NULL : rxn)::Ptr{Cint}, S_t::Ptr{Float64},
+                                    (S_u === nothing ? C_NULL : S_u)::Ptr{Float64}, u::Ptr{Float64},
+                                    stats::Ptr{Float64}, nbad::Ref{Clonglong})::Cint)
+    return S_t, S_u, u, stats, nbad[]
+end
 
 # ---------------------------------------------------------------------------------------------
 # host mechanism compiler and batch.xml reader of libbrhip.so (C++; br_mech_parse, br_read_batch_xml):
@@ -416,6 +454,28 @@ function batch_reactor_ensemble(md::DeviceMech, T::AbstractVector, p::AbstractVe
     return X, U[md.ng+1:end, :], stats
 end
 
+"""ignition_sensitivity: d ln t_ign / d ln k_r of N reactors (T, p, inlet composition and end time each)
+to the selected reactions, the native route for what a `sens=true` caller of the reference would do by
+re-solving with perturbed parameters on the host. `reactions`: 1-based indices into the mechanism's
+reactions (gas reactions in mechanism order, then surface reactions), `nothing` = all. Returns
+(S [nsel x N], t_ign [N], nbad): S[j, i] is NaN where a perturbed run failed or did not ignite."""
+function ignition_sensitivity(md::DeviceMech, T::AbstractVector, p::AbstractVector, comps::AbstractVector, tf;
+                              Asv=1.0, factor::Real=2.0, reactions=nothing, rtol::Real=1e-6, atol::Real=1e-10)
+    N = length(T)
+    U = zeros(ncomp(md), N)
+    for i in 1:N
+        U[:, i] = initial_state(md, T[i], p[i], comps[i])
+    end
+    fillv(v) = v isa AbstractVector ? collect(Float64, v) : fill(Float64(v), N)
+    ign = ignition_species(md)
+    ign > 0 || error("ignition_sensitivity: the mechanism has no OH (the ignition marker)")
+    opts = BrOpts(rtol=rtol, atol=atol, ignition_species=ign)
+    rxn = reactions === nothing ? nothing : Cint[r - 1 for r in reactions]
+    S, _, _, stats, nbad = sensitivity(md.m, collect(Float64, T), fillv(Asv), U, fillv(tf), md.nrg + md.nrs;
+                                       factor=factor, rxn=rxn, opts=opts)
+    return S, stats[17, :], nbad
+end
+
 """The ensemble over several GPUs (br_integrate_multi): `mechs[d]` created on device d."""
 function integrate_multi!(mechs::Vector{Ptr{Cvoid}}, T, Asv, u::Matrix{Float64}, tf; opts::BrOpts=BrOpts())
     N = length(T)
@@ -561,6 +621,7 @@ function batch_reactor(input_file::AbstractString, lib_dir::AbstractString, user
 end
 
 export batch_reactor, batch_reactor_ensemble, compile_mechanism, read_batch_xml, DeviceMech, Chemistry,
-       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!
+       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!, with_rate_mult, sensitivity,
+       ignition_sensitivity
 
 end # module
