@@ -300,9 +300,9 @@ __device__ __forceinline__ void stage_tables(const DevMech& M, char* dst) {
 }
 
 // Per-reactor rate multipliers (br_opts.rate_mult): m = mult[row(rid)][reaction], applied to the T-only
-// constants of the three engines' init functions and nowhere else. A launch with multipliers sets bit 0
-// of DevMech::g_par (the table is 8-byte aligned); the MultBlock then sits in the 32 bytes in front of
-// the table. No kernel argument, DevMech field or KOpts field of its own: any of them moves the kernel
+// constants (gas_tconst, surf_tconst, and k_lane's own init) and nowhere else. A launch with multipliers
+// sets bit 0 of DevMech::g_par (the table is 8-byte aligned); the MultBlock then sits in the 32 bytes in
+// front of the table. No kernel argument, DevMech field or KOpts field of its own: any of them moves the kernel
 // arguments, which has changed the register allocation of kernels that never read the new one
 // (brhip_ctl.hpp, tout_tag). The table is in the caller's reaction order: gas reactions as in
 // br_mech_desc, then surface reactions. `perm` maps a packed gas position (mech_pack's evaluation order:
@@ -340,6 +340,8 @@ __device__ __forceinline__ MultRow mult_row(int rid) {
     return r;
 }
 
+#include "brhip_chem.hpp"   // the chemistry: what the loops below, and the group engines', evaluate
+
 // T-only constants (src/BatchReactor.jl:14-17: T is a per-reactor constant); g/RT scratch in accw.
 // rid: the reactor's index in the launch (its row of rate multipliers). MULT = false: the parity kernels
 // (k_rates, k_rhs, k_jac), whose entry points take no br_opts and never see a tagged g_par
@@ -351,60 +353,13 @@ __device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, con
     double* grt = R.sp + Lay<CPL>::ACCW;
     if (lane == 0) R.sp[Lay<CPL>::ONE] = 1.0;
 #pragma unroll 1
-    for (int k = lane; k < MF(ng); k += WAVE) {
-        const double* c = MF(nasa) + 15 * k;
-        const double* a = (T < c[0]) ? c + 8 : c + 1;
-        const double h = a[0] + a[1] * T / 2 + a[2] * T * T / 3 + a[3] * T * T * T / 4 + a[4] * T * T * T * T / 5 + a[5] / T;
-        const double s = a[0] * lT + a[1] * T + a[2] * T * T / 2 + a[3] * T * T * T / 3 + a[4] * T * T * T * T / 4 + a[6];
-        grt[k] = h - s;
-    }
+    for (int k = lane; k < MF(ng); k += WAVE) grt[k] = nasa_grt(k, T, lT);
     wave_sync();
     const double RT = R_GAS * T;
 #pragma unroll 1
-    for (int r = lane; r < MF(nrg); r += WAVE) {
-        const auto rec = rx_rec(tb.rx, r);
-        const uint32_t info = rec[2];
-        const double* gp = (MULT ? gpar_table() : MF(g_par)) + 4 * r;
-        const double kf1 = gp[0] * exp(gp[1] * lT - gp[2] / T);
-        const double kf = (MULT && mr.on()) ? kf1 * mr.gas(r) : kf1;   // (kr = kf / Kc: both directions scale)
-        double kr = 0.0;
-        if (gi_rev(info)) {
-            double dg = 0.0;
-            const int nf = gi_nf(info), nr = gi_nr(info);
-            for (int e = 0; e < 4; ++e) if (e < nr) dg += grt[sp8(rec[1], e)];
-            for (int e = 0; e < 4; ++e) if (e < nf) dg -= grt[sp8(rec[0], e)];
-            double Kc = exp(-dg) * pow(MF(p_std) / RT, (double)MF(g_dnu)[r]);
-            Kc *= gp[3];
-            kr = kf / Kc;
-        }
-        R.rxd[2 * r] = kf;
-        R.rxd[2 * r + 1] = kr;
-        if (gi_tb(info) == 2) {
-            const int fi = gi_foidx(info);
-            const double* fp = MF(fo_par) + 8 * fi;
-            double* fo = R.fod + 4 * fi;
-            fo[0] = fp[0] * exp(fp[1] * lT - fp[2] / T) / kf1;   // k0 / k_inf (of the unscaled pair)
-            double fcv = 1.0;
-            if (gi_troe(info)) {
-                fcv = (1 - fp[3]) * exp(-T / fp[4]) + fp[3] * exp(-T / fp[5]);
-                if (gi_troe(info) == 4) fcv += exp(-fp[6] / T);
-            }
-            const double lfc = log10(fcv);
-            fo[1] = lfc;
-            fo[2] = ((MF(conv) & BR_CONV_TROE_C4) ? -4.0 : -0.4) - 0.67 * lfc;
-            fo[3] = 0.75 - 1.27 * lfc;
-        }
-    }
+    for (int r = lane; r < MF(nrg); r += WAVE) gas_tconst<MULT>(tb, r, grt, T, lT, RT, mr, R.rxd, R.fod);
 #pragma unroll 1
-    for (int r = lane; r < MF(nrs); r += WAVE) {
-        const uint32_t info = tb.sx[SX_WORDS * r + 4];
-        const double* sp = MF(s_par) + 4 * r;
-        double k;
-        if (si_stick(info)) k = sp[0] * sqrt(RT / (2 * M_PI * sp[3]));
-        else k = sp[0] * pow(T, sp[1]) * exp(-sp[2] / RT);
-        if (MULT && mr.on()) k *= mr.surf(r);
-        R.skd[2 * r] = k;
-    }
+    for (int r = lane; r < MF(nrs); r += WAVE) R.skd[2 * r] = surf_tconst<MULT>(tb, r, T, RT, mr);
     // the RXD stores reach L2 and this CU's L1 is invalidated before any lane reads the slot
     // (it held the previous reactor's constants)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -412,63 +367,13 @@ __device__ __forceinline__ void init_tconst(const DevMech& M, const Tab& tb, con
     wave_sync();
 }
 
-// falloff: fac = Pr/(1+Pr)*F and d fac / d[M] (CHEMKIN Lindemann / Troe); fo[0] = k0/k_inf
-// (T-only, so Pr = fo[0] [M] needs no division). Troe: log10 F = log10 Fcent / (1 + f1^2) with
-// f1 = x / den, evaluated as log10 Fcent den^2 / (den^2 + x^2) (one division), F = exp10(...)
-// instead of the generic pow(10, .) (same value to an ulp, about half the instructions).
-__device__ __forceinline__ double troe_F(double Pr, const double* fo, double& x_out, double& den_out) {
-    const double Prs = Pr > 1e-300 ? Pr : 1e-300;
-    const double x = log10(Prs) + fo[2];
-    const double den = fo[3] - 0.14 * x;
-    const double d2 = den * den;
-    x_out = x; den_out = den;
-    return exp10(fo[1] * d2 / (d2 + x * x));
-}
-template <bool WANT_D>
-__device__ __forceinline__ void falloff(const double* fo, bool troe, double Mc, double& fac, double& dfac) {
-    const double k0r = fo[0];
-    const double Pr = k0r * Mc;
-    double F = 1.0, g = 0.0;
-    if (troe) {
-        double x, den;
-        F = troe_F(Pr, fo, x, den);
-        if (WANT_D) {
-            const double lfc = fo[1], nn = fo[3];
-            const double f1 = x / den;
-            const double df1 = nn / (den * den);
-            g = -lfc * 2 * f1 / ((1 + f1 * f1) * (1 + f1 * f1)) * df1;
-        }
-    }
-    fac = Pr / (1 + Pr) * F;
-    if (WANT_D) dfac = (F / ((1 + Pr) * (1 + Pr)) + F * g / (1 + Pr)) * k0r;
-}
-
-// third-body concentrations of the efficiency sets: mc[s] = Ctot + sum (eff-1) c over the set's
-// list (one lane per set; the list entries are read 2 at a time so the loads overlap)
+// third-body concentrations of the efficiency sets: mc[s], one lane per set
 template <int CPL>
 __device__ __forceinline__ void third_body_sets(const DevMech& M, const Tab& tb_, double* sp, double Ctot, int lane) {
     const Tab tb = tab_view<CPL>(br_lds, M);
     const double* conc = sp + Lay<CPL>::CONC;
 #pragma unroll 1
-    for (int t = lane; t < MF(nset); t += WAVE) {
-        const uint32_t w = tb.tbs[t];
-        const int b = w & 0xFFFFF, e = b + (int)(w >> 20);
-        double s0 = Ctot, s1 = 0.0;
-        int i = b;
-#pragma unroll 1
-        for (; i + 1 < e; i += 2) {
-            const double2 e0 = *reinterpret_cast<const double2*>(tb.tbe + 16 * i);
-            const double2 e1 = *reinterpret_cast<const double2*>(tb.tbe + 16 * (i + 1));
-            const int k0 = __double_as_longlong(e0.x) & 0xFFFF, k1 = __double_as_longlong(e1.x) & 0xFFFF;
-            s0 = fma(e0.y, conc[k0], s0);
-            s1 = fma(e1.y, conc[k1], s1);
-        }
-        if (i < e) {
-            const double2 e0 = *reinterpret_cast<const double2*>(tb.tbe + 16 * i);
-            s0 = fma(e0.y, conc[__double_as_longlong(e0.x) & 0xFFFF], s0);
-        }
-        sp[Lay<CPL>::MC + t] = s0 + s1;
-    }
+    for (int t = lane; t < MF(nset); t += WAVE) sp[Lay<CPL>::MC + t] = third_body_sum(tb, t, conc, Ctot);
 }
 
 // rates of progress, accumulated straight into the per-species production sums:
@@ -498,28 +403,7 @@ __device__ __forceinline__ void production(const DevMech& M, const Tab& tb_, con
     const double* conc = R.sp + L::CONC;
     double* accw = R.sp + L::ACCW;
     double* accs = R.sp + L::ACCS;
-    // net rate of progress of gas reaction r (mass action x third body / falloff)
-    auto rate = [&](int r, const uint4& ra, const double2 k) -> double {
-        const uint32_t info = ra.z;
-        const int tbk = gi_tb(info);
-        // branch-free mass-action products: unused slots point at conc[L::ONE] = 1; mechanisms
-        // with at most 3 reactants / products per reaction (MF(nu4) == 0, GRI) skip the 4th slot
-        double Pf = (conc[sp8(ra.x, 0)] * conc[sp8(ra.x, 1)]) * conc[sp8(ra.x, 2)];
-        double Pb = (conc[sp8(ra.y, 0)] * conc[sp8(ra.y, 1)]) * conc[sp8(ra.y, 2)];
-        if (MF(nu4)) { Pf *= conc[sp8(ra.x, 3)]; Pb *= conc[sp8(ra.y, 3)]; }
-        double D = k.x * Pf - k.y * Pb;
-        if (tbk) {
-            const double Mc = R.sp[L::MC + gi_tbidx(info)];
-            if (tbk == 1) D *= Mc;
-            else {
-                double fac, dfac;
-                falloff<false>(R.fod + 4 * gi_foidx(info), gi_troe(info) != 0, Mc, fac, dfac);
-                D *= fac;
-                if (xm) D *= Mc * 1e-6;                                // [M] in mol/cm3
-            }
-        }
-        return D;
-    };
+    const double* mc = R.sp + L::MC;
     // two reactions per lane and iteration (r and r + 64): their LDS gather chains overlap; the
     // next iteration's {kf, kr} loads are issued one iteration ahead
     const int nrg = MF(nrg);
@@ -537,8 +421,8 @@ __device__ __forceinline__ void production(const DevMech& M, const Tab& tb_, con
         const uint4 rb0 = *reinterpret_cast<const uint4*>(rr0.b);
         const uint4 ra1 = *reinterpret_cast<const uint4*>(rr1.a);
         const uint4 rb1 = *reinterpret_cast<const uint4*>(rr1.b);
-        const double D0 = rate(r, ra0, k0);
-        const double D1 = rate(q1, ra1, k1);
+        const double D0 = gas_rate(conc, mc, R.fod, k0, ra0.x, ra0.y, ra0.z, xm);
+        const double D1 = gas_rate(conc, mc, R.fod, k1, ra1.x, ra1.y, ra1.z, xm);
         scatter(accw, rb0.x, rb0.y, rb0.z, rb0.w, D0);
         if (has1) scatter(accw, rb1.x, rb1.y, rb1.z, rb1.w, D1);
     }
@@ -549,15 +433,8 @@ __device__ __forceinline__ void production(const DevMech& M, const Tab& tb_, con
         const double* xe = tb.sxe + SXE_DOUBLES * r;
         // k(T) times the constant site factors (Gamma/sigma per surface reactant, 1 for sticking)
         double k = R.skd[2 * r] * xe[4];
-        if (nc) {
-            const uint32_t cs = rec[5];
-            double s = 0.0;
-            for (int j = 0; j < 4; ++j) if (j < nc) s += xe[j] * conc[sp8(cs, j)];
-            k *= exp(-s / RT);
-        }
-        // branch-free product over up to 6 reactants (pad slots = conc[L::ONE] = 1)
-        const double P = ((conc[sp8(rec[0], 0)] * conc[sp8(rec[0], 1)]) * (conc[sp8(rec[0], 2)] * conc[sp8(rec[0], 3)])) *
-                         (conc[sp8(rec[1], 0)] * conc[sp8(rec[1], 1)]);
+        if (nc) k *= surf_cov_factor(rec[5], nc, xe, conc, RT);
+        const double P = surf_product(rec, conc);
         scatter(accs, rec[6], rec[7], rec[8], rec[9], k * P);
     }
 }
@@ -822,23 +699,14 @@ __device__ __forceinline__ void jacobian(const DevMech& M, const Tab& tb_, const
     for (int r = lane; r < MF(nrg); r += WAVE) {                   // per-reaction multipliers
         const auto rec = rx_rec(tb.rx, r);
         const uint32_t info = rec[2];
-        const int nf = gi_nf(info), nr = gi_nr(info), tbk = gi_tb(info);
+        const int nf = gi_nf(info), nr = gi_nr(info);
         const double kf = R.rxd[2 * r], kr = R.rxd[2 * r + 1];
-        double Pf = 1.0, Pb = 1.0;
+        double Pf = 1.0, Pb = 1.0;   // (a running product from 1: not gas_mass_action's (c0 c1) c2)
         for (int e = 0; e < 4; ++e) if (e < nf) Pf *= conc[sp8(rec[0], e)];
         for (int e = 0; e < 4; ++e) if (e < nr) Pb *= conc[sp8(rec[1], e)];
         const double D = kf * Pf - kr * Pb;
-        double pre = 1.0, coefM = 0.0;
-        if (tbk) {
-            const double Mc = R.sp[L::MC + gi_tbidx(info)];
-            if (tbk == 1) { pre = Mc; coefM = 1.0; }
-            else {
-                double fac, dfac;
-                falloff<true>(R.fod + 4 * gi_foidx(info), gi_troe(info) != 0, Mc, fac, dfac);
-                pre = fac * (xm ? Mc * 1e-6 : 1.0);
-                coefM = dfac * (xm ? Mc * 1e-6 : 1.0) + (xm ? fac * 1e-6 : 0.0);
-            }
-        }
+        double pre, coefM;
+        gas_pre_coef(info, R.sp + L::MC, R.fod, xm, pre, coefM);
         jscr[2 * r] = pre;
         jscr[2 * r + 1] = D * coefM;
     }
@@ -847,11 +715,7 @@ __device__ __forceinline__ void jacobian(const DevMech& M, const Tab& tb_, const
         const uint32_t* rec = tb.sx + SX_WORDS * r;
         const int nc = si_ncov(rec[4]);
         double k = R.skd[2 * r];
-        if (nc) {
-            double s = 0.0;
-            for (int j = 0; j < 4; ++j) if (j < nc) s += tb.sxe[SXE_DOUBLES * r + j] * conc[sp8(rec[5], j)];
-            k *= exp(-s / RT);
-        }
+        if (nc) k *= surf_cov_factor(rec[5], nc, tb.sxe + SXE_DOUBLES * r, conc, RT);
         R.skd[2 * r + 1] = k;
     }
     __builtin_amdgcn_s_waitcnt(0);   // scratch stores complete before other lanes read them
@@ -877,23 +741,9 @@ __device__ __forceinline__ void jacobian(const DevMech& M, const Tab& tb_, const
                 double* acc = (i >= c2) ? mcb : (i >= c1) ? accs : accw;
                 const auto rec = rx_rec(tb.rx, r);
                 const uint32_t info = rec[2];
-                const int nf = gi_nf(info), nr = gi_nr(info), tbk = gi_tb(info);
+                const int tbk = gi_tb(info);
                 const double pre = ld_l2(jscr + 2 * r);
-                double d = 0.0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nf && sp8(rec[0], e) == j) {
-                    double pr = R.rxd[2 * r];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) if (e2 != e && e2 < nf) pr *= conc[sp8(rec[0], e2)];
-                    d += pre * pr;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nr && sp8(rec[1], e) == j) {
-                    double pr = R.rxd[2 * r + 1];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) if (e2 != e && e2 < nr) pr *= conc[sp8(rec[1], e2)];
-                    d -= pre * pr;
-                }
+                double d = gas_dq_dc(rec, r, j, conc, R.rxd, pre);
                 if (tbk && j < MF(ng)) d += ld_l2(jscr + 2 * r + 1) * MF(tb_eff)[gi_tbidx(info) * n + j];
                 scatter(acc, rec[4], rec[5], rec[6], rec[7], d);
             }
@@ -931,61 +781,17 @@ __device__ __forceinline__ void jacobian(const DevMech& M, const Tab& tb_, const
                 const int r = rr;
                 const auto rec = rx_rec(tb.rx, r);
                 const uint32_t info = rec[2];
-                const int nf = gi_nf(info), nr = gi_nr(info), tbk = gi_tb(info);
+                const int tbk = gi_tb(info);
                 const double pre = ld_l2(jscr + 2 * r);
-                double d = 0.0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nf && sp8(rec[0], e) == j) {
-                    double pr = R.rxd[2 * r];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) if (e2 != e && e2 < nf) pr *= conc[sp8(rec[0], e2)];
-                    d += pre * pr;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nr && sp8(rec[1], e) == j) {
-                    double pr = R.rxd[2 * r + 1];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) if (e2 != e && e2 < nr) pr *= conc[sp8(rec[1], e2)];
-                    d -= pre * pr;
-                }
+                double d = gas_dq_dc(rec, r, j, conc, R.rxd, pre);
                 if (tbk && j < MF(ng)) d += ld_l2(jscr + 2 * r + 1) * MF(tb_eff)[gi_tbidx(info) * MF(n) + j];
                 scatter(accw, rec[4], rec[5], rec[6], rec[7], d);
             } else {
                 const int r = rr - MF(nrg);
                 const uint32_t* rec = tb.sx + SX_WORDS * r;
                 const uint32_t info = rec[4];
-                const int nf = si_nf(info), nc = si_ncov(info);
-                const bool stick = si_stick(info);
                 const double k = R.skd[2 * r + 1];
-                double cv[6], dc[6];
-                int sp[6];
-#pragma unroll
-                for (int e = 0; e < 6; ++e) {
-                    sp[e] = e < nf ? (e < 4 ? sp8(rec[0], e) : sp8(rec[1], e - 4)) : -1;
-                    cv[e] = 1.0; dc[e] = 0.0;
-                    if (e < nf) {
-                        const int s = sp[e];
-                        if (s < MF(ng)) { cv[e] = conc[s]; dc[e] = 1.0 / tb.molwt[s]; }
-                        else if (stick) { cv[e] = conc[s]; dc[e] = 1.0; }
-                        else { cv[e] = conc[s] * MF(G) / tb.sigma[s]; dc[e] = MF(G) / tb.sigma[s]; }
-                    }
-                }
-                double d = 0.0;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) if (sp[e] == j) {
-                    double pr = k;
-#pragma unroll
-                    for (int e2 = 0; e2 < 6; ++e2) if (e2 != e && e2 < nf) pr *= cv[e2];
-                    d += pr * dc[e];
-                }
-                if (nc) {
-                    double P = 1.0;
-#pragma unroll
-                    for (int e = 0; e < 6; ++e) if (e < nf) P *= cv[e];
-                    const double q = k * P;
-                    for (int jj = 0; jj < 4; ++jj) if (jj < nc && sp8(rec[5], jj) == j)
-                        d += q * (-tb.sxe[SXE_DOUBLES * r + jj] / RT);
-                }
+                const double d = surf_dq_du(tb, rec, info, tb.sxe + SXE_DOUBLES * r, j, k, conc, RT, MF(ng), MF(G));
                 scatter(accs, rec[6], rec[7], rec[8], rec[9], d);
             }
         }
@@ -996,10 +802,7 @@ __device__ __forceinline__ void jacobian(const DevMech& M, const Tab& tb_, const
             const bool act = k < MF(n);
             const double w = act ? accw[k] : 0.0;
             const double sf = act ? accs[k] : 0.0;
-            const double Mk = tb.molwt[k];
-            double v;
-            if (k < MF(ng)) v = (j < MF(ng) ? Mk * w / tb.molwt[j] : 0.0) + Mk * Asv * sf;
-            else v = Asv_th * tb.sigma[k] / MF(G) * sf;
+            const double v = jac_entry(tb, k, j, MF(ng), MF(G), tb.molwt[k], w, sf, Asv, Asv_th);
             if (k < JW) Jsave[j * JW + k] = act ? v : 0.0;
         }
         wave_sync();

@@ -107,109 +107,50 @@ __device__ __forceinline__ double group_bcast(double v) {
     }
 }
 
-// T-only constants of one group's reactor (init_tconst for the group layout): {kf, kr} per gas
-// reaction into kd, falloff constants into fod, k(T) per surface reaction into skd; g/RT per gas
-// species in the ACCW slots (scratch)
+// T-only constants of one group's reactor: {kf, kr} per gas reaction into kd, falloff constants into
+// fod, k(T) per surface reaction into skd; g/RT per gas species in the ACCW slots (scratch)
 template <int GL>
 __device__ __forceinline__ void g_init_tconst(const Tab& tb, double* sp, QKd* kd, double* fod, double* skd, double T,
                                               int gl, int rid = 0) {
     typedef grp::GLay<GL> L;
-    const MultRow mr = mult_row(rid);   // the reactor's rate multipliers (br_opts.rate_mult), as init_tconst
+    const MultRow mr = mult_row(rid);   // the reactor's rate multipliers (br_opts.rate_mult)
     const double lT = log(T);
     double* grt = sp + L::ACCW;
     const int ng = MF(ng), nrg = MF(nrg), nrs = MF(nrs);
     if (gl == 0) sp[L::ONE] = 1.0;
-    if (gl < ng) {
-        const double* c = MF(nasa) + 15 * gl;
-        const double* a = (T < c[0]) ? c + 8 : c + 1;
-        const double h = a[0] + a[1] * T / 2 + a[2] * T * T / 3 + a[3] * T * T * T / 4 + a[4] * T * T * T * T / 5 + a[5] / T;
-        const double s = a[0] * lT + a[1] * T + a[2] * T * T / 2 + a[3] * T * T * T / 3 + a[4] * T * T * T * T / 4 + a[6];
-        grt[gl] = h - s;
-    }
+    if (gl < ng) grt[gl] = nasa_grt(gl, T, lT);
     wave_sync();
     const double RT = R_GAS * T;
 #pragma unroll 1
-    for (int r = gl; r < nrg; r += GL) {
-        const auto rec = rx_rec(tb.rx, r);
-        const uint32_t info = rec[2];
-        const double* gp = gpar_table() + 4 * r;
-        const double kf1 = gp[0] * exp(gp[1] * lT - gp[2] / T);
-        const double kf = mr.on() ? kf1 * mr.gas(r) : kf1;
-        double kr = 0.0;
-        if (gi_rev(info)) {
-            double dg = 0.0;
-            const int nf = gi_nf(info), nr = gi_nr(info);
-            for (int e = 0; e < 4; ++e) if (e < nr) dg += grt[sp8(rec[1], e)];
-            for (int e = 0; e < 4; ++e) if (e < nf) dg -= grt[sp8(rec[0], e)];
-            double Kc = exp(-dg) * pow(MF(p_std) / RT, (double)MF(g_dnu)[r]);
-            Kc *= gp[3];
-            kr = kf / Kc;
-        }
-        kd[2 * r] = kf;
-        kd[2 * r + 1] = kr;
-        if (gi_tb(info) == 2) {
-            const int fi = gi_foidx(info);
-            const double* fp = MF(fo_par) + 8 * fi;
-            double* fo = fod + 4 * fi;
-            fo[0] = fp[0] * exp(fp[1] * lT - fp[2] / T) / kf1;
-            double fcv = 1.0;
-            if (gi_troe(info)) {
-                fcv = (1 - fp[3]) * exp(-T / fp[4]) + fp[3] * exp(-T / fp[5]);
-                if (gi_troe(info) == 4) fcv += exp(-fp[6] / T);
-            }
-            const double lfc = log10(fcv);
-            fo[1] = lfc;
-            fo[2] = ((MF(conv) & BR_CONV_TROE_C4) ? -4.0 : -0.4) - 0.67 * lfc;
-            fo[3] = 0.75 - 1.27 * lfc;
-        }
-    }
+    for (int r = gl; r < nrg; r += GL) gas_tconst<true>(tb, r, grt, T, lT, RT, mr, kd, fod);
 #pragma unroll 1
-    for (int r = gl; r < nrs; r += GL) {                               // as init_tconst
-        const uint32_t info = tb.sx[SX_WORDS * r + 4];
-        const double* spr = MF(s_par) + 4 * r;
-        double k;
-        if (si_stick(info)) k = spr[0] * sqrt(RT / (2 * M_PI * spr[3]));
-        else k = spr[0] * pow(T, spr[1]) * exp(-spr[2] / RT);
-        if (mr.on()) k *= mr.surf(r);
-        skd[r] = k;
-    }
+    for (int r = gl; r < nrs; r += GL) skd[r] = surf_tconst<true>(tb, r, T, RT, mr);
     // the kd stores reach L2 and this CU's L1 is invalidated before any lane reads the slot (it held
-    // the previous reactor's constants), as init_tconst's RXD
+    // the previous reactor's constants)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     wave_sync();
 }
 
-// the mass-action part kf prod(c_f) - kr prod(c_b) of gas reaction r of a group (products in the
-// wavefront engine's order; pad slots read conc[ONE] = 1), the reactant / product concentrations
-// kept for the Jacobian
-template <int GL>
-__device__ __forceinline__ double g_mass_action_k(const double* sp, double2 k, uint32_t w0, uint32_t w1,
-                                                  double (&cf)[4], double (&cb)[4]) {
-    typedef grp::GLay<GL> L;
+// the mass-action part kf prod(c_f) - kr prod(c_b) of a gas reaction of a group: gas_mass_action's
+// products, with the 4th slots read before MF(nu4) is tested (kept apart: the two forms compile to
+// different loads, the values are the same)
+__device__ __forceinline__ double g_mass_action_k(const double* conc, double2 k, uint32_t w0, uint32_t w1) {
+    double cf[4], cb[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        cf[e] = sp[L::CONC + sp8(w0, e)];
-        cb[e] = sp[L::CONC + sp8(w1, e)];
+        cf[e] = conc[sp8(w0, e)];
+        cb[e] = conc[sp8(w1, e)];
     }
     double Pf = (cf[0] * cf[1]) * cf[2], Pb = (cb[0] * cb[1]) * cb[2];
     if (MF(nu4)) { Pf *= cf[3]; Pb *= cb[3]; }
     return k.x * Pf - k.y * Pb;
 }
-// {kf, kr} of gas reaction r: one 16-byte load
-__device__ __forceinline__ double2 g_kpair(const QKd* kd, int r) {
-    return make_double2(kd[2 * r], kd[2 * r + 1]);   // (16-B aligned: one dwordx4 load)
-}
-template <int GL>
-__device__ __forceinline__ double g_mass_action(const double* sp, const QKd* kd, uint32_t w0, uint32_t w1, int r,
-                                                double (&cf)[4], double (&cb)[4]) {
-    return g_mass_action_k<GL>(sp, g_kpair(kd, r), w0, w1, cf, cb);
-}
 
 // residual! (src/BatchReactor.jl:312-376) of a group's reactor: du of component gl (gas rates
 // :355, surface rates :344, du assembly with the Asv quirk :345,:363-373); the pressure of this
-// evaluation to *p_out (save_data semantics). Same arithmetic order as the wavefront engine's rhs()
-// (concentrations, third-body pairing, rate products, falloff, surface coverage factor).
+// evaluation to *p_out (save_data semantics). The chemistry is brhip_chem.hpp's, as in the wavefront
+// engine's rhs(); the concentrations c_k = u_k / M_k and the du assembly are in its order.
 template <int GL>
 __device__ __forceinline__ double g_rhs(const Tab& tb, double* sp, const QKd* kd, const double* fod, const double* skd,
                                         double T, double Asv, double Asv_th, double u, int gl, double* p_out) {
@@ -219,8 +160,8 @@ __device__ __forceinline__ double g_rhs(const Tab& tb, double* sp, const QKd* kd
     // the {kf, kr} pairs of this lane's first two gas reactions, issued before the concentration and
     // third-body setup so their latency overlaps it (kd is in global memory)
     const double2 kz = make_double2(0.0, 0.0);
-    const double2 kp0 = nrg > 0 ? g_kpair(kd, gl < nrg ? gl : 0) : kz;
-    const double2 kp1 = nrg > GL ? g_kpair(kd, gl + GL < nrg ? gl + GL : 0) : kz;
+    const double2 kp0 = nrg > 0 ? kpair(kd, gl < nrg ? gl : 0) : kz;
+    const double2 kp1 = nrg > GL ? kpair(kd, gl + GL < nrg ? gl + GL : 0) : kz;
     const double Mk = tb.molwt[gl];
     const double c = gl < n ? (gas ? u / Mk : u) : 0.0;              // c_k = u_k / M_k; coverages as is
     sp[L::CONC + gl] = c;
@@ -231,27 +172,11 @@ __device__ __forceinline__ double g_rhs(const Tab& tb, double* sp, const QKd* kd
     wave_sync();
     const double* conc = sp + L::CONC;
 #pragma unroll 1
-    for (int t = gl; t < nset; t += GL) {                              // third-body sums per efficiency set
-        const uint32_t w = tb.tbs[t];                                  // (pairing as third_body_sets)
-        const int b = w & 0xFFFFF, e = b + (int)(w >> 20);
-        double s0 = Ctot, s1 = 0.0;
-        int i = b;
-#pragma unroll 1
-        for (; i + 1 < e; i += 2) {
-            const double2 e0 = *reinterpret_cast<const double2*>(tb.tbe + 16 * i);
-            const double2 e1 = *reinterpret_cast<const double2*>(tb.tbe + 16 * (i + 1));
-            s0 = fma(e0.y, conc[__double_as_longlong(e0.x) & 0xFFFF], s0);
-            s1 = fma(e1.y, conc[__double_as_longlong(e1.x) & 0xFFFF], s1);
-        }
-        if (i < e) {
-            const double2 e0 = *reinterpret_cast<const double2*>(tb.tbe + 16 * i);
-            s0 = fma(e0.y, conc[__double_as_longlong(e0.x) & 0xFFFF], s0);
-        }
-        sp[L::MC + t] = s0 + s1;
-    }
+    for (int t = gl; t < nset; t += GL) sp[L::MC + t] = third_body_sum(tb, t, conc, Ctot);
     wave_sync();
     double* accw = sp + L::ACCW;
     double* accs = sp + L::ACCS;
+    const double* mc = sp + L::MC;
     const bool xm = (MF(conv) & 2) != 0;
     int it = 0;   // (uniform: the pass index)
 #pragma unroll 1
@@ -259,39 +184,22 @@ __device__ __forceinline__ double g_rhs(const Tab& tb, double* sp, const QKd* kd
         const auto rr = rx_rec(tb.rx, r);
         const uint4 ra = *reinterpret_cast<const uint4*>(rr.a);
         const uint4 rb = *reinterpret_cast<const uint4*>(rr.b);
-        double cf[4], cb[4];
         double2 kp;
         if (it == 0) kp = kp0;
         else if (it == 1) kp = kp1;
-        else kp = g_kpair(kd, r);
-        double D = g_mass_action_k<GL>(sp, kp, ra.x, ra.y, cf, cb);
-        const int tbk = gi_tb(ra.z);
-        if (tbk) {                                                     // as production()'s rate
-            const double Mc = sp[L::MC + gi_tbidx(ra.z)];
-            if (tbk == 1) D *= Mc;
-            else {
-                double fac, dfac;
-                falloff<false>(fod + 4 * gi_foidx(ra.z), gi_troe(ra.z) != 0, Mc, fac, dfac);
-                D *= fac;
-                if (xm) D *= Mc * 1e-6;                                // [M] in mol/cm3
-            }
-        }
+        else kp = kpair(kd, r);
+        const double D = gas_third_body(g_mass_action_k(conc, kp, ra.x, ra.y), gi_tb(ra.z), ra.z, mc, fod, xm);
         scatter(accw, rb.x, rb.y, rb.z, rb.w, D);
     }
     const double RT = R_GAS * T;
 #pragma unroll 1
-    for (int r = gl; r < nrs; r += GL) {                               // surface reactions (production())
+    for (int r = gl; r < nrs; r += GL) {                               // surface reactions
         const uint32_t* rec = tb.sx + SX_WORDS * r;
         const int nc = si_ncov(rec[4]);
         const double* xe = tb.sxe + SXE_DOUBLES * r;
-        double k = skd[r] * xe[4];
-        if (nc) {
-            double s = 0.0;
-            for (int j = 0; j < 4; ++j) if (j < nc) s += xe[j] * conc[sp8(rec[5], j)];
-            k *= exp(-s / RT);
-        }
-        const double P = ((conc[sp8(rec[0], 0)] * conc[sp8(rec[0], 1)]) * (conc[sp8(rec[0], 2)] * conc[sp8(rec[0], 3)])) *
-                         (conc[sp8(rec[1], 0)] * conc[sp8(rec[1], 1)]);
+        double k = skd[r] * xe[4];   // k(T) times the constant site factors
+        if (nc) k *= surf_cov_factor(rec[5], nc, xe, conc, RT);
+        const double P = surf_product(rec, conc);
         scatter(accs, rec[6], rec[7], rec[8], rec[9], k * P);
     }
     wave_sync();
@@ -331,6 +239,7 @@ __device__ __forceinline__ void g_jac_cols(const Tab& tb, double* sp, const QKd*
     const double* conc = sp + L::CONC;
     double* accw = sp + L::ACCW;
     double* accs = sp + L::ACCS;
+    const double* mc = sp + L::MC;
     const double Mk = tb.molwt[gl];
     const int* cp = MF(col_ptr);
     const int* cr = MF(col_rx);
@@ -347,78 +256,22 @@ __device__ __forceinline__ void g_jac_cols(const Tab& tb, double* sp, const QKd*
                 const int r = rr;
                 const auto rec = rx_rec(tb.rx, r);
                 const uint32_t info = rec[2];
-                const int nf = gi_nf(info), nr = gi_nr(info), tbk = gi_tb(info);
-                double cf[4], cb4[4];
-                const double D = g_mass_action<GL>(sp, kd, rec[0], rec[1], r, cf, cb4);
-                double pre = 1.0, coefM = 0.0;
-                if (tbk) {
-                    const double Mc = sp[L::MC + gi_tbidx(info)];
-                    if (tbk == 1) { pre = Mc; coefM = 1.0; }
-                    else {
-                        double fac, dfac;
-                        falloff<true>(fod + 4 * gi_foidx(info), gi_troe(info) != 0, Mc, fac, dfac);
-                        pre = fac * (xm ? Mc * 1e-6 : 1.0);
-                        coefM = dfac * (xm ? Mc * 1e-6 : 1.0) + (xm ? fac * 1e-6 : 0.0);
-                    }
-                }
-                double d = 0.0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nf && sp8(rec[0], e) == j) {
-                    double pr = kd[2 * r];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) if (e2 != e && e2 < nf) pr *= conc[sp8(rec[0], e2)];
-                    d += pre * pr;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nr && sp8(rec[1], e) == j) {
-                    double pr = kd[2 * r + 1];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) if (e2 != e && e2 < nr) pr *= conc[sp8(rec[1], e2)];
-                    d -= pre * pr;
-                }
+                const int tbk = gi_tb(info);
+                const double D = g_mass_action_k(conc, kpair(kd, r), rec[0], rec[1]);
+                double pre, coefM;
+                gas_pre_coef(info, mc, fod, xm, pre, coefM);
+                double d = gas_dq_dc(rec, r, j, conc, kd, pre);
                 if (tbk && j < ng) d += (D * coefM) * MF(tb_eff)[gi_tbidx(info) * n + j];
                 scatter(accw, rec[4], rec[5], rec[6], rec[7], d);
             } else {                                                     // surface reaction: dq/du_j
                 const int r = rr - nrg;
                 const uint32_t* rec = tb.sx + SX_WORDS * r;
                 const uint32_t info = rec[4];
-                const int nf = si_nf(info), nc = si_ncov(info);
-                const bool stick = si_stick(info);
+                const int nc = si_ncov(info);
                 const double* eps = tb.sxe + SXE_DOUBLES * r;
                 double k = skd[r];
-                if (nc) {
-                    double s = 0.0;
-                    for (int jj = 0; jj < 4; ++jj) if (jj < nc) s += eps[jj] * conc[sp8(rec[5], jj)];
-                    k *= exp(-s / RT);
-                }
-                double cv[6], dc[6];
-                int spe[6];
-#pragma unroll
-                for (int e = 0; e < 6; ++e) {
-                    spe[e] = e < nf ? (e < 4 ? sp8(rec[0], e) : sp8(rec[1], e - 4)) : -1;
-                    cv[e] = 1.0; dc[e] = 0.0;
-                    if (e < nf) {
-                        const int s = spe[e];
-                        if (s < ng) { cv[e] = conc[s]; dc[e] = 1.0 / tb.molwt[s]; }
-                        else if (stick) { cv[e] = conc[s]; dc[e] = 1.0; }
-                        else { cv[e] = conc[s] * Gs / tb.sigma[s]; dc[e] = Gs / tb.sigma[s]; }
-                    }
-                }
-                double d = 0.0;
-#pragma unroll
-                for (int e = 0; e < 6; ++e) if (spe[e] == j) {
-                    double pr = k;
-#pragma unroll
-                    for (int e2 = 0; e2 < 6; ++e2) if (e2 != e && e2 < nf) pr *= cv[e2];
-                    d += pr * dc[e];
-                }
-                if (nc) {
-                    double P = 1.0;
-#pragma unroll
-                    for (int e = 0; e < 6; ++e) if (e < nf) P *= cv[e];
-                    const double q = k * P;
-                    for (int jj = 0; jj < 4; ++jj) if (jj < nc && (int)sp8(rec[5], jj) == j) d += q * (-eps[jj] / RT);
-                }
+                if (nc) k *= surf_cov_factor(rec[5], nc, eps, conc, RT);
+                const double d = surf_dq_du(tb, rec, info, eps, j, k, conc, RT, ng, Gs);
                 scatter(accs, rec[6], rec[7], rec[8], rec[9], d);
             }
         }
@@ -426,9 +279,7 @@ __device__ __forceinline__ void g_jac_cols(const Tab& tb, double* sp, const QKd*
         const bool act = gl < n;
         const double w = act ? accw[gl] : 0.0;
         const double sf = (act && nrs) ? accs[gl] : 0.0;
-        double v;
-        if (gl < ng) v = (j < ng ? Mk * w / tb.molwt[j] : 0.0) + Mk * Asv * sf;
-        else v = Asv_th * tb.sigma[gl] / Gs * sf;
+        const double v = jac_entry(tb, gl, j, ng, Gs, Mk, w, sf, Asv, Asv_th);
         jst(j, act ? v : 0.0);
         wave_sync();
     }
