@@ -10,9 +10,11 @@ from .engine import Engine, STAT_FIELDS, integrate_multi, phase_grid
 from .reactor import (Chemistry, ConstantParams, ODEProblem, UserDefinedState, batch_reactor, batch_reactor_ensemble,
                       batch_reactor_programmatic, compile_mechanism, julia_string)
 from . import _lib
+from . import tprog
+from .tprog import TemperatureProgram
 
 __all__ = ["Mechanism", "MechanismError", "Engine", "Chemistry", "ConstantParams", "ODEProblem", "UserDefinedState",
            "julia_string", "integrate_multi", "phase_grid", "batch_reactor", "batch_reactor_ensemble",
            "batch_reactor_programmatic", "compile_mechanism", "read_batch_xml", "read_chemkin",
            "read_surface_xml", "read_therm", "STAT_FIELDS", "CONV_KC_UNIT_SLIP", "CONV_FALLOFF_XM",
-           "CONV_DOC_COVG", "CONV_TROE_C4", "CONV_REFERENCE"]
+           "CONV_DOC_COVG", "CONV_TROE_C4", "CONV_REFERENCE", "TemperatureProgram"]

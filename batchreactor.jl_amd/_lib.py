@@ -29,6 +29,7 @@ class Opts(C.Structure):
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_steps", C.c_int), ("device", C.c_int),
                 ("hmax", C.c_double), ("trace_cap", C.c_int), ("unstable_factor", C.c_double),
                 ("ignition_species", C.c_int), ("nout", C.c_int), ("tout", dp), ("yout", dp),
+                ("ntprog", C.c_int), ("tprog_t", dp), ("tprog_T", dp), ("ntprog_rows", C.c_int), ("tprog_row", ip),
                 ("dq_jacobian", C.c_int), ("nmult", C.c_int), ("rate_mult", dp), ("rate_mult_row", ip),
                 ("tout_per_reactor", C.c_int)]
 
@@ -51,7 +52,7 @@ EXPORTS = ["br_version", "br_last_error", "br_device_count", "br_mech_create", "
            "br_last_kernel_ms", "br_debug_lu_solve", "br_mech_parse", "br_host_mech_desc", "br_host_mech_sizes",
            "br_host_mech_species", "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml",
            "br_integrate_host", "br_phase_tout_dev", "br_integrate_phase", "br_debug_group_eval",
-           "br_debug_group_lu_solve", "br_sensitivity"]
+           "br_debug_group_lu_solve", "br_sensitivity", "br_debug_tprog_eval"]
 
 # br_integrate_host callbacks: int f(void* user, double t, const double* u, double* du);
 # void cb(void* user, double t, const double* u)
@@ -96,6 +97,8 @@ def lib():
     L.br_debug_group_eval.restype = C.c_int
     L.br_debug_group_lu_solve.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, ip, ip]
     L.br_debug_group_lu_solve.restype = C.c_int
+    L.br_debug_tprog_eval.argtypes = [C.c_int, C.c_int, dp, dp, C.c_int, ip, C.c_int, dp, dp]
+    L.br_debug_tprog_eval.restype = C.c_int
     cs = C.c_char_p
     L.br_mech_parse.argtypes = [cs, cs, cs, cs, C.c_int, C.POINTER(vp)]
     L.br_host_mech_desc.argtypes = [vp, C.POINTER(MechDesc)]
@@ -127,7 +130,7 @@ def dptr(a):
 
 
 def iptr(a):
-    return a.ctypes.data_as(ip)
+    return a.ctypes.data_as(ip) if a is not None else None
 
 
 def integrate_host(f, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, on_step=None):

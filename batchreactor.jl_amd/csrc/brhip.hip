@@ -15,6 +15,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/brhip.h"
@@ -26,6 +27,7 @@ namespace {
 #include "brhip_lane.hpp"   // one reactor per lane (small gas mechanisms)
 #include "brhip_group.hpp"   // group engines: 4 / 2 reactors per wave (16- / 32-lane groups, n <= 32)
 #include "brhip_sens.hpp"    // rate-multiplier block, br_sensitivity's expansion and reduction kernels
+#include "brhip_tprog.hpp"   // temperature programmes T(t): the launch's block and the evaluator
 
 // ------------------------------------------------------------------------------------
 // the integrator kernel: one reactor per 64-lane wavefront, `rpb` reactors per workgroup
@@ -66,11 +68,14 @@ constexpr size_t LDS_PER_CU = 160 * 1024, LDS_GRANULE = 1280;   // gfx950 (granu
 __host__ __device__ constexpr int br_wpe(int nmax) {
     return nmax == 32 ? BR_WPE32 : (nmax == 56 || nmax == 64) ? BR_WPE56 : nmax == 72 ? BR_WPE72 : BR_WPE;
 }
-template <int NMAX>
+// TPROG: the instances of a temperature-programme run (br_opts.ntprog; brhip_tprog.hpp). They take KOptsProg,
+// do not read Tv, and refresh the T-only constants inside the step loop; everything under
+// `if constexpr (TPROG)` is theirs alone, the isothermal instances compile the source they always had.
+template <int NMAX, bool TPROG = false>
 __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_per_eu(br_wpe(NMAX), 8))) void k_integrate(
     DevMech M, int N, int rpb, const double* __restrict__ Tv, const double* __restrict__ Asvv, double* __restrict__ U,
-    const double* __restrict__ tfv, KOpts o, br_stats* __restrict__ stats, double* __restrict__ Jws,
-    double* __restrict__ trace) {
+    const double* __restrict__ tfv, std::conditional_t<TPROG, KOptsProg, KOpts> o, br_stats* __restrict__ stats,
+    double* __restrict__ Jws, double* __restrict__ trace) {
     constexpr int CPL = NMAX > 64 ? 2 : 1;   // components per lane
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const WaveCtx W = wave_ctx<CPL, NMAX>(M, smem_raw, rpb, Jws);
@@ -97,7 +102,17 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     VA<CPL, 64, vec_stride(NMAX)> V = Vm;
     const RView& S = W.R;
     const int n = M.n;
-    const double T = Tv[rid];
+    // T: the temperature the T-only constants in the reactor's slots were built for. Isothermal: the
+    // reactor's constant. Programme run: T(t) of the last refresh, wave-uniform, with the reactor's row
+    // and cached segment in tp
+    double T;
+    [[maybe_unused]] std::conditional_t<TPROG, TProgRow, NoTProgRow> tp;
+    if constexpr (TPROG) {
+        tp = tprog_row(o.prog, rid);
+        T = uni(tp.eval(o.rid_t0 ? uni(o.rid_t0[idx]) : 0.0));
+    } else {
+        T = Tv[rid];
+    }
     const double Asv = Asvv ? Asvv[rid] : 1.0;
     const double Asv_th = (M.conv & 4) ? 1.0 : Asv;
     double* Jsave = Jws + (size_t)widx * ws_doubles(NMAX, M.nrg);   // J, LU factors, Jacobian scratch
@@ -182,6 +197,21 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     LDSd* scr = (LDSd*)(S.sp + Lay<CPL>::ACCW);   // solve / LU scratch: the production sums are idle then
     double* p_last = reinterpret_cast<double*>(W.rbase);
     int dqj = -1;   // >= 0: building DQ Jacobian column dqj (this RHS is at y + inc_dqj e_dqj)
+    // Programme run, before an RHS or Jacobian evaluation: T at the time the controller means
+    // (ctl_rhs_time). Bitwise the cached T: the constants stand (the DQ columns and Newton iterations of
+    // an attempt share its tn, a constant programme never changes). Else the isothermal prologue's
+    // init_tconst for the new T, fences included: {kf, kr} live in the global slot. Its g/RT scratch is
+    // the production sums' block, idle between evaluations (the RHS zeroes it, the solve is done with it).
+    auto tprog_refresh = [&]() {
+        if constexpr (TPROG) {
+            const double Tt = uni(tp.eval(uni(ctl_rhs_time(C))));
+            if (__double_as_longlong(Tt) != __double_as_longlong(T)) {
+                T = Tt;
+                wave_sync();
+                init_tconst<CPL, true>(M, tb, S, T, lane, rid);
+            }
+        }
+    };
     for (;;) {
         double y[CPL], f[CPL];
 #pragma unroll
@@ -194,6 +224,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         }
         {
             BR_CLK(c0);
+            tprog_refresh();
             rhs<CPL>(M, tb, S, T, Asv, Asv_th, y, lane, p_last, f);
             BR_X_AFTER_RHS();
             BR_ACC(cyc_rhs, c0);
@@ -228,6 +259,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         if (act_code == A_SETUP) {
             if (!jac_ready && ui(C->newj)) {
                 BR_CLK(c0);
+                tprog_refresh();   // (the tn of the RHS just before: no refresh in practice)
                 jacobian<CPL>(M, tb, S, T, Asv, Asv_th, y, lane, Jsave, jscr);
                 BR_X_AFTER_JAC();
                 BR_ACC(cyc_jac, c0);
@@ -407,6 +439,11 @@ static const void* wave_kernel(int nmax) {   // one reactor per wavefront
          : nmax == 56 ? (const void*)k_integrate<56> : nmax == 64 ? (const void*)k_integrate<64>
                                                                   : (const void*)k_integrate<72>;
 }
+static const void* wave_tprog_kernel(int nmax) {   // ... of a temperature-programme run
+    return nmax == 16 ? (const void*)k_integrate<16, true> : nmax == 32 ? (const void*)k_integrate<32, true>
+         : nmax == 56 ? (const void*)k_integrate<56, true> : nmax == 64 ? (const void*)k_integrate<64, true>
+                                                                        : (const void*)k_integrate<72, true>;
+}
 static const void* lane_kernel(int nm) { return nm == 9 ? (const void*)k_lane<9> : (const void*)k_lane<12>; }
 // the parity kernels, by components per lane
 static const void* rates_kernel(int cpl) { return cpl == 2 ? (const void*)k_rates<2> : (const void*)k_rates<1>; }
@@ -504,7 +541,7 @@ struct Stage {
 
 extern "C" {
 
-int br_version(void) { return 210; }   // 210: br_opts grew (rate multipliers before tout_per_reactor)
+int br_version(void) { return 220; }   // 220: br_opts grew (temperature programmes between yout and dq_jacobian)
 const char* br_last_error(void) { return g_err.c_str(); }
 int br_device_count(void) {
     int c = 0;
@@ -800,6 +837,76 @@ static void stage_mult(Stage& st, const br_mech* m, int N, const br_opts* opts, 
     }
 }
 
+// temperature programmes of a br_opts (ntprog > 0): the shape checks every entry point shares
+static int tprog_shape(int N, int ntprog, const double* t, const double* T, int nrows, const int* row) {
+    if (ntprog < 0 || !t || !T || nrows < 1)
+        return fail(BR_ERR_INPUT, "ntprog > 0 needs tprog_t and tprog_T [ntprog_rows][ntprog], ntprog_rows >= 1");
+    if (!row && nrows != N)
+        return fail(BR_ERR_INPUT, "tprog_row is NULL: ntprog_rows must be N = " + std::to_string(N) + ", got " +
+                                      std::to_string(nrows));
+    return 0;
+}
+static int tprog_request(int N, const br_opts* opts) {
+    if (!opts || opts->ntprog == 0) return 0;
+    return tprog_shape(N, opts->ntprog, opts->tprog_t, opts->tprog_T, opts->ntprog_rows, opts->tprog_row);
+}
+// ... and the contents, for host arrays. A row: first time 0, times ascending, NaN only as trailing padding,
+// temperatures at the knots finite and > 0. The message names the first reactor that has a bad row index
+// or uses a bad row, and the row (i0: the index of reactor 0 in the caller's ensemble)
+static std::string tprog_row_defect(int nk, const double* t, const double* T) {
+    if (!(t[0] == 0.0)) return "its first knot time is " + std::to_string(t[0]) + ", not 0";
+    bool pad = false;
+    for (int j = 0; j < nk; ++j) {
+        if (t[j] != t[j]) { pad = true; continue; }
+        if (pad) return "knot time " + std::to_string(j) + " follows a NaN (NaN is trailing padding only)";
+        if (j && !(t[j] >= t[j - 1])) return "knot times must be ascending (knot " + std::to_string(j) + ")";
+        if (!(t[j] < INFINITY)) return "knot time " + std::to_string(j) + " is not finite";
+        if (!(T[j] > 0.0) || !(T[j] < INFINITY))
+            return "T = " + std::to_string(T[j]) + " at knot " + std::to_string(j) + ": temperatures must be finite and > 0";
+    }
+    return "";
+}
+static int check_tprog_arrays(int N, int nk, const double* t, const double* T, int nrows, const int* row) {
+    if (const int rc = tprog_shape(N, nk, t, T, nrows, row)) return rc;
+    std::vector<std::string> defect(nrows);
+    for (int r = 0; r < nrows; ++r) defect[r] = tprog_row_defect(nk, t + (size_t)r * nk, T + (size_t)r * nk);
+    for (int i = 0; i < N; ++i) {
+        const int r = row ? row[i] : i;
+        if (r < 0 || r >= nrows)
+            return fail(BR_ERR_INPUT, "tprog_row[" + std::to_string(i) + "] = " + std::to_string(r) +
+                                          " is outside [0, ntprog_rows = " + std::to_string(nrows) + "): reactor " + std::to_string(i));
+        if (!defect[r].empty())
+            return fail(BR_ERR_INPUT, "temperature programme of reactor " + std::to_string(i) + " (row " + std::to_string(r) +
+                                          "): " + defect[r]);
+    }
+    for (int r = 0; r < nrows; ++r)   // (a row no reactor uses is checked all the same)
+        if (!defect[r].empty())
+            return fail(BR_ERR_INPUT, "temperature programme row " + std::to_string(r) + " (used by no reactor): " + defect[r]);
+    return 0;
+}
+static int check_tprog_host(int N, const br_opts* opts) {
+    if (!opts || opts->ntprog == 0) return 0;
+    return check_tprog_arrays(N, opts->ntprog, opts->tprog_t, opts->tprog_T, opts->ntprog_rows, opts->tprog_row);
+}
+// doubles of staging the host programme arrays take (times, temperatures, then the row indices as ints), and the
+// copy: od's pointers become the device ones
+static size_t tprog_stage_doubles(int N, const br_opts* opts) {
+    if (!opts || opts->ntprog <= 0) return 0;
+    return 2 * (size_t)opts->ntprog_rows * opts->ntprog + (opts->tprog_row ? ((size_t)N + 1) / 2 : 0);
+}
+static void stage_tprog(Stage& st, int N, const br_opts* opts, br_opts* od) {
+    if (!opts || opts->ntprog <= 0) return;
+    const size_t ne = (size_t)opts->ntprog_rows * opts->ntprog;
+    od->tprog_t = st.push(opts->tprog_t, ne);
+    od->tprog_T = st.push(opts->tprog_T, ne);
+    if (opts->tprog_row) {
+        int* drow = (int*)st.take(((size_t)N + 1) / 2);
+        const hipError_t e = hipMemcpy(drow, opts->tprog_row, (size_t)N * sizeof(int), hipMemcpyHostToDevice);
+        if (st.err == hipSuccess) st.err = e;
+        od->tprog_row = drow;
+    }
+}
+
 // the kernel options of a run: br_opts with its defaults filled in (no work list, no deferral)
 static KOpts make_kopts(const br_mech* m, const br_opts* opts, bool traced) {
     KOpts o;
@@ -824,21 +931,28 @@ static KOpts make_kopts(const br_mech* m, const br_opts* opts, bool traced) {
 }
 
 // k_integrate on `nwg` workgroups of m->rpb reactors (waves) each
+// (prog: a temperature-programme run, the k_integrate<NMAX, true> instance with KOptsProg = o + the block)
 static int launch_wave(br_mech* m, const DevMech& dm, int N, int nwg, const double* dT, const double* dAsv, double* du,
-                       const double* dtf, const KOpts& o, br_stats* dstats, double* trace, hipStream_t s) {
-    const void* fn = wave_kernel(m->nmax);
+                       const double* dtf, const KOpts& o, br_stats* dstats, double* trace, hipStream_t s,
+                       const TProg* prog = nullptr) {
+    const void* fn = prog ? wave_tprog_kernel(m->nmax) : wave_kernel(m->nmax);
     HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->shmem));
     const int rpb = m->rpb;
     double* jws = m->jws.as<double>();
-    void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf, (void*)&o,
-                    (void*)&dstats, (void*)&jws, (void*)&trace};
+    KOptsProg op;
+    static_cast<KOpts&>(op) = o;
+    if (prog) op.prog = *prog;
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf,
+                    prog ? (void*)&op : (void*)&o, (void*)&dstats, (void*)&jws, (void*)&trace};
     HIPCHK(hipLaunchKernel(fn, dim3(nwg), dim3(64 * rpb), args, m->shmem, s));
     return 0;
 }
 
 static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv, double* du, const double* dtf,
                          const br_opts* opts, br_stats* dstats, void* stream, double* trace) {
-    if (!m || N < 0 || !dT || !du || !dtf) return fail(BR_ERR_INPUT, "bad argument");
+    const bool prog = opts && opts->ntprog != 0;   // a temperature programme: dT is not read
+    if (!m || N < 0 || (!dT && !prog) || !du || !dtf) return fail(BR_ERR_INPUT, "bad argument");
+    if (const int rc = tprog_request(N, opts)) return rc;
     if (N == 0) return 0;
     HIPCHK(hipSetDevice(m->device));
     KOpts o = make_kopts(m, opts, trace != nullptr);
@@ -852,7 +966,8 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
         HIPCHK(hipGetLastError());
         dm.g_par = reinterpret_cast<const double*>(reinterpret_cast<size_t>(dm.g_par) | 1u);
     }
-    const int engine = trace ? 0 : pick_engine(m);   // traced runs: the wavefront engine
+    const int engine = (trace || prog) ? 0 : pick_engine(m);   // traced and programme runs: the wavefront engine
+    const TProg tp = prog ? TProg{opts->tprog_t, opts->tprog_T, opts->tprog_row, opts->ntprog, 0} : TProg{};
     if (engine < 0) {
         // 2 or 4 reactors per wave (one per 32- / 16-lane group), persistent grid over the resident
         // workgroups, reactors from a work counter
@@ -926,7 +1041,7 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
         o.work = m->wq.as<int>();
     }
     HIPCHK(hipEventRecord(m->ev0, s));
-    const int rc = launch_wave(m, dm, N, nwg, dT, dAsv, du, dtf, o, dstats, trace, s);
+    const int rc = launch_wave(m, dm, N, nwg, dT, dAsv, du, dtf, o, dstats, trace, s, prog ? &tp : nullptr);
     if (rc) return rc;
     HIPCHK(hipEventRecord(m->ev1, s));
     m->ev_recorded = true;
@@ -967,7 +1082,10 @@ static int check_tout_rows(int N, int nout, const double* tout) {
 
 static int integrate_host(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                           const br_opts* opts, br_stats* stats, double* trace) {
-    if (!m || N < 0 || !T || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
+    // (the programme first: its checks need no handle, and with one the T argument may be NULL)
+    if (N >= 0) { if (const int rc = check_tprog_host(N, opts)) return rc; }
+    const bool prog = opts && opts->ntprog != 0;
+    if (!m || N < 0 || (!T && !prog) || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
     if (N == 0) return 0;
     HIPCHK(hipSetDevice(m->device));
     const int n = m->n;
@@ -987,7 +1105,8 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
         if (!(opts->tout[i] >= opts->tout[i - 1])) return fail(BR_ERR_INPUT, "tout must be ascending");
     if (const int rc = check_mult_host(m, N, opts)) return rc;
     Stage st;
-    HIPCHK(st.reserve(m, (size_t)N * (3 + n + BR_NSTAT) + ntr + nto + nyo + mult_stage_doubles(m, N, opts)));
+    HIPCHK(st.reserve(m, (size_t)N * (3 + n + BR_NSTAT) + ntr + nto + nyo + mult_stage_doubles(m, N, opts) +
+                             tprog_stage_doubles(N, opts)));
     double* dT = st.take(N);
     double* dA = st.take(N);
     double* dtf = st.take(N);
@@ -1002,6 +1121,7 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
         od.yout = dyo = st.push(opts->yout, nyo);
     }
     stage_mult(st, m, N, opts, &od);
+    stage_tprog(st, N, opts, &od);
     st.put(dT, T, N);
     st.put(dA, Asv, N);
     st.put(dtf, tf, N);
@@ -1031,7 +1151,9 @@ int br_integrate_traced(br_mech* m, int N, const double* T, const double* Asv, d
 
 int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, const double* Asv, double* u,
                        const double* tf, const br_opts* opts, br_stats* stats) {
-    if (!mechs || ndev < 1 || N < 0 || !T || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
+    if (N >= 0) { if (const int rc0 = check_tprog_host(N, opts)) return rc0; }   // (indices of the ensemble in the message)
+    const bool prog = opts && opts->ntprog != 0;
+    if (!mechs || ndev < 1 || N < 0 || (!T && !prog) || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
     for (int d = 0; d < ndev; ++d) {
         if (!mechs[d] || mechs[d]->n != mechs[0]->n) return fail(BR_ERR_INPUT, "handles differ in size");
         for (int e = 0; e < d; ++e)
@@ -1062,7 +1184,15 @@ int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, 
                 if (opts->rate_mult_row) od.rate_mult_row = opts->rate_mult_row + start;
                 else { od.rate_mult = opts->rate_mult + (size_t)start * nr; od.nmult = cnt; }
             }
-            rc[d] = integrate_host(mechs[d], cnt, T + start, Asv ? Asv + start : nullptr, u + (size_t)start * n,
+            if (prog) {   // likewise the programmes: the slice's row indices, or its rows
+                if (opts->tprog_row) od.tprog_row = opts->tprog_row + start;
+                else {
+                    od.tprog_t = opts->tprog_t + (size_t)start * opts->ntprog;
+                    od.tprog_T = opts->tprog_T + (size_t)start * opts->ntprog;
+                    od.ntprog_rows = cnt;
+                }
+            }
+            rc[d] = integrate_host(mechs[d], cnt, T ? T + start : nullptr, Asv ? Asv + start : nullptr, u + (size_t)start * n,
                                    tf + start, opts ? &od : nullptr, stats ? stats + start : nullptr, nullptr);
             if (rc[d]) msg[d] = g_err;
         });
@@ -1086,7 +1216,9 @@ int br_phase_tout_dev(int N, br_stats* dstats, int ntau, const double* dtau, con
 
 int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                        const br_opts* opts, br_stats* stats, int ntau, const double* tau, double* tout, double* yout) {
-    if (!m || N < 0 || !T || !u || !tf || !tau || !tout || !yout || ntau < 1) return fail(BR_ERR_INPUT, "bad argument");
+    if (N >= 0) { if (const int rcp = check_tprog_host(N, opts)) return rcp; }
+    const bool prog = opts && opts->ntprog != 0;
+    if (!m || N < 0 || (!T && !prog) || !u || !tf || !tau || !tout || !yout || ntau < 1) return fail(BR_ERR_INPUT, "bad argument");
     if (!opts || opts->ignition_species < 1 || opts->ignition_species > m->ng)
         return fail(BR_ERR_INPUT, "br_integrate_phase needs br_opts.ignition_species (the phases are multiples of t_ign)");
     for (int j = 0; j < ntau; ++j)
@@ -1098,7 +1230,8 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
     const size_t nu = (size_t)N * n, nto = (size_t)N * ntau, nyo = nto * n;
     if (const int rcm = check_mult_host(m, N, opts)) return rcm;
     Stage st;
-    HIPCHK(st.reserve(m, (size_t)N * (3 + BR_NSTAT) + 2 * nu + ntau + nto + nyo + mult_stage_doubles(m, N, opts)));
+    HIPCHK(st.reserve(m, (size_t)N * (3 + BR_NSTAT) + 2 * nu + ntau + nto + nyo + mult_stage_doubles(m, N, opts) +
+                             tprog_stage_doubles(N, opts)));
     double* dT = st.push(T, N);
     double* dA = st.push(Asv, N);
     double* dtf = st.push(tf, N);
@@ -1110,6 +1243,7 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
     double* dyo = st.push(yout, nyo);   // (rows without an output keep their values)
     br_opts od = *opts;
     stage_mult(st, m, N, opts, &od);   // (both passes run with the same multipliers)
+    stage_tprog(st, N, opts, &od);     // (... and the same programmes)
     HIPCHK(st.err);
     od.trace_cap = 0;
     // pass 1: no outputs, for t_ign
@@ -1139,6 +1273,8 @@ constexpr size_t SENS_BUDGET_BYTES = (size_t)1 << 30;   // expanded inputs, stat
 int br_sensitivity(br_mech* m, int N, const double* T, const double* Asv, const double* u0, const double* tf,
                    const br_opts* opts, double factor, int nsel, const int* rxn, double* S_tign, double* S_u, double* u,
                    br_stats* stats, long long* nbad) {
+    if (opts && opts->ntprog != 0)   // (before anything else: no handle, no device needed to learn it)
+        return fail(BR_ERR_UNSUPPORTED, "br_sensitivity does not take a temperature programme (br_opts.ntprog)");
     if (!m || N < 0 || !T || !u0 || !tf) return fail(BR_ERR_INPUT, "bad argument");
     if (!(factor > 1.0) || !(factor < INFINITY)) return fail(BR_ERR_INPUT, "factor must be finite and > 1");
     if (opts && (opts->nmult != 0 || opts->rate_mult))

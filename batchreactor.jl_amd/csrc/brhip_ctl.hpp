@@ -830,6 +830,23 @@ __device__ __forceinline__ void begin_step(LCtl* C, VA<CPL, GW, VS>& V, int lane
     BR_SUB_ADD(7, bt0);
 }
 
+// The time CVODE hands to f for the RHS evaluation the controller has just asked for (A_RHS), read
+// from the controller's own state, where ctl_post_rhs / ctl_post_solve left it:
+//   PH_F0      tn = t0: the first evaluation;
+//   PH_HIN     tn + hg: cvYddNorm's f(tn + hg, y) of the initial-step estimate, hg as ctl_post_rhs set it
+//              with the y of that evaluation (tn is still t0);
+//   PH_NEWTON  tn: cv_predict advanced it (clamped to tstop) for the predictor and every Newton
+//              evaluation of the attempt, cv_restore took it back to saved_t after a failed one; the DQ
+//              columns and the analytic Jacobian of a setup are at the same tn;
+//   PH_EF1     tn: the restored time (cvDoErrorTest's f(tn, zn[0]) before the order-1 restart).
+// Only a temperature-programme run evaluates f at a time (k_integrate<NMAX, true>); a field for it in
+// Ctl would move every engine's LDS block.
+template <int GW = 64>
+__device__ __forceinline__ double ctl_rhs_time(LCtl* C) {
+    const double tn = ud(C->tn);
+    return gui<GW>(C->phase) == PH_HIN ? tn + ud(C->hg) : tn;
+}
+
 // Controller, part 1: after the RHS value f = F(y) of this lane is known.
 // Returns A_RHS (next y in V[V_Y]), A_SOLVE (delta for the solve returned in *rhs_out),
 // A_SETUP (Jacobian decision in C->newj, then LU and solve), A_DONE.

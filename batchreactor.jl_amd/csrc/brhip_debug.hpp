@@ -241,6 +241,34 @@ extern "C" int br_debug_group_lu_solve(int gl, int nm, int N, int n, const doubl
     return 0;
 }
 
+// temperature-programme check: k_tprog_eval (brhip_tprog.hpp), the integrator's evaluator, on host arrays
+// that pass the checks of the host entry points
+extern "C" int br_debug_tprog_eval(int N, int ntprog, const double* tprog_t, const double* tprog_T, int nrows,
+                                   const int* tprog_row, int nt, const double* t, double* Tout) {
+    if (N <= 0 || ntprog < 1 || nt < 1 || !t || !Tout) return fail_code_input();
+    if (const int rc = check_tprog_arrays(N, ntprog, tprog_t, tprog_T, nrows, tprog_row)) return rc;
+    const size_t nk = (size_t)nrows * ntprog, ne = (size_t)N * nt;
+    double *dkt, *dkT, *dt, *dTo;
+    int* drow = nullptr;
+    DevScratch S;
+    HIPCHK(S.alloc(&dkt, nk * 8));
+    HIPCHK(S.alloc(&dkT, nk * 8));
+    HIPCHK(S.alloc(&dt, ne * 8));
+    HIPCHK(S.alloc(&dTo, ne * 8));
+    HIPCHK(hipMemcpy(dkt, tprog_t, nk * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dkT, tprog_T, nk * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dt, t, ne * 8, hipMemcpyHostToDevice));
+    if (tprog_row) {
+        HIPCHK(S.alloc(&drow, (size_t)N * 4));
+        HIPCHK(hipMemcpy(drow, tprog_row, (size_t)N * 4, hipMemcpyHostToDevice));
+    }
+    const TProg p{dkt, dkT, drow, ntprog, 0};
+    hipLaunchKernelGGL(k_tprog_eval, dim3((N + 63) / 64), dim3(64), 0, 0, N, p, nt, (const double*)dt, dTo);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(Tout, dTo, ne * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 #if BR_PHASE_CLOCKS
 // diagnostic build only (not declared in brhip.h): read and reset the 16 sub-phase clock sums
 // (BR_SUB_ADD slots of brhip_device.hpp)

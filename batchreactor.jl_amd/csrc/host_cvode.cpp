@@ -39,7 +39,7 @@ struct HostCvode {
     void* user;
     double rtol, atol;
     std::vector<double> zn[LMAX + 1];
-    std::vector<double> ewt, y, acor, tempv, ftemp, delta, savedJ, A, fdq;
+    std::vector<double> ewt, y, acor, tempv, tempv2, ftemp, delta, savedJ, A, fdq;
     std::vector<int> piv;
     double tn = 0, h = 0, hprime = 0, hscale = 0, eta = 1, etamax = ETAMX1, hmin = 0, hu = 0, tstop = 0;
     double tau[LMAX + 1] = {}, tq[6] = {}, l[LMAX] = {};
@@ -62,8 +62,9 @@ struct HostCvode {
         for (int i = 0; i < n; ++i) { const double t = x[i] * ewt[i]; s += t * t; }
         return std::sqrt(s / n);
     }
-    void rhs(const double* u, double* du) {
-        if (f(user, tn, u, du) != 0) rhs_fail = 1;
+    // f at time t: the time CVODE hands to f (tn everywhere but cvYddNorm's f(tn + hg, y) in cvHin)
+    void rhs(double t, const double* u, double* du) {
+        if (f(user, t, u, du) != 0) rhs_fail = 1;
     }
     void set_ewt(const double* u) {
         for (int i = 0; i < n; ++i) ewt[i] = 1.0 / (rtol * std::fabs(u[i]) + atol);
@@ -113,7 +114,7 @@ struct HostCvode {
             const double ys = yy[j];
             const double inc = std::max(srur * std::fabs(ys), mininc / ewt[j]);
             yy[j] += inc;
-            rhs(yy.data(), fdq.data());
+            rhs(tn, yy.data(), fdq.data());
             ++nfe_dq;
             yy[j] = ys;
             const double ii = 1.0 / inc;
@@ -241,7 +242,7 @@ struct HostCvode {
     }
     void residual(const std::vector<double>& ycor) {
         for (int i = 0; i < n; ++i) y[i] = zn[0][i] + ycor[i];
-        rhs(y.data(), ftemp.data());
+        rhs(tn, y.data(), ftemp.data());
         ++nfe;
         for (int i = 0; i < n; ++i) delta[i] = (rl1 * zn[1][i] + ycor[i]) - gamma * ftemp[i];
     }
@@ -358,6 +359,7 @@ struct HostCvode {
     // cvStep: 0 accepted, < 0 failure (CVODE flags)
     int step(double hmax_inv) {
         const double saved_t = tn;
+        tempv2 = zn[0];                // the accepted state, for an RHS failure
         int ncf = 0, nef = 0, nflag = FIRST_CALL;
         double dsm = 0;
         if (nst > 0 && hprime != h) {
@@ -373,7 +375,11 @@ struct HostCvode {
             predict();
             set_coeffs();
             const int r = newton(nflag);
-            if (rhs_fail) return -8;   // CV_RHSFUNC_FAIL
+            if (rhs_fail) {            // CV_RHSFUNC_FAIL: back to the last accepted state and time
+                restore(saved_t);
+                zn[0] = tempv2;        // (the accepted state itself: predict and restore round)
+                return BR_ERR_RHS;
+            }
             if (r != 0) {   // cvHandleNFlag
                 ++ncfn;
                 restore(saved_t);
@@ -413,8 +419,9 @@ struct HostCvode {
             h *= eta;
             hscale = h;
             qwait = LONG_WAIT;
-            rhs(zn[0].data(), tempv.data());
+            rhs(tn, zn[0].data(), tempv.data());   // (tn: restored above)
             ++nfe;
+            if (rhs_fail) { zn[0] = tempv2; return BR_ERR_RHS; }
             for (int i = 0; i < n; ++i) zn[1][i] = h * tempv[i];
         }
         complete_step();
@@ -437,8 +444,9 @@ struct HostCvode {
         double hnew = hg;
         for (int count = 1; count <= MAX_ITERS; ++count) {
             for (int i = 0; i < n; ++i) y[i] = hg * zn[1][i] + zn[0][i];
-            rhs(y.data(), tempv.data());
+            rhs(tn + hg, y.data(), tempv.data());   // cvYddNorm: f(tn + hg, y)
             ++nfe;
+            if (rhs_fail) return;
             for (int i = 0; i < n; ++i) tempv[i] = (tempv[i] - zn[1][i]) * (1.0 / hg);
             const double yddnrm = wrms(tempv.data());
             if (ok || count == MAX_ITERS) { hnew = hg; break; }
@@ -470,12 +478,15 @@ extern "C" int br_integrate_host(int n, br_rhs_fn f, void* user, double* u, doub
     std::copy(u, u + n, cv.zn[0].begin());
     if (cb) cb(cb_user, 0.0, u);   // save_data at t0
     cv.set_ewt(cv.zn[0].data());
-    cv.rhs(cv.zn[0].data(), cv.zn[1].data());
+    cv.rhs(cv.tn, cv.zn[0].data(), cv.zn[1].data());
     ++cv.nfe;
     int status = 0;
-    if (cv.rhs_fail) status = -8;
+    if (cv.rhs_fail) status = BR_ERR_RHS;
     if (!status) {
         cv.initial_step(tf);
+        if (cv.rhs_fail) status = BR_ERR_RHS;   // (inside cvHin: the state is still u0 at t0)
+    }
+    if (!status) {
         if ((cv.tn + cv.h - cv.tstop) * cv.h > 0.0) cv.h = (cv.tstop - cv.tn) * (1.0 - 4.0 * UROUND);
         cv.hscale = cv.h;
         cv.hprime = cv.h;

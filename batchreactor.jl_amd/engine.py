@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import tprog as _tprog
 from .mechanism import Mechanism
 
 STAT_FIELDS = ("nsteps", "nfe", "nje", "nsetups", "nni", "ncfn", "netf", "status", "cyc_total", "cyc_rhs",
@@ -195,18 +196,23 @@ class Engine:
         return rate_mult_table(rate_mult, rate_mult_row, N, self.nr)
 
     def _opts(self, rtol, atol, max_steps, trace_cap=0, unstable_factor=0.0, tout=None, yout=None, dq_jacobian=False,
-              mult=None, mult_row=None):
+              mult=None, mult_row=None, prog=None):
         nout = 0 if tout is None else tout.shape[-1]   # tout: [nout], or [N, nout] (one row per reactor)
         o = _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout,
-                      _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, int(dq_jacobian),
+                      _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, dq_jacobian=int(dq_jacobian),
                       tout_per_reactor=int(nout > 0 and tout.ndim == 2))
         if mult is not None:   # (arrays from rate_mult_table; the caller keeps them alive for the call)
             o.nmult, o.rate_mult = mult.shape[0], _lib.dptr(mult)
             o.rate_mult_row = _lib.iptr(mult_row) if mult_row is not None else None
+        if prog is not None and prog[0] is not None:   # (kt, kT, rows) from tprog.table, kept alive by the caller
+            kt, kT, rows = prog
+            o.ntprog, o.ntprog_rows = kt.shape[1], kt.shape[0]
+            o.tprog_t, o.tprog_T, o.tprog_row = _lib.dptr(kt), _lib.dptr(kT), _lib.iptr(rows)
         return o
 
     def integrate(self, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, trace_cap=0, tout=None,
-                  unstable_factor=0.0, dq_jacobian=False, rate_mult=None, rate_mult_row=None):
+                  unstable_factor=0.0, dq_jacobian=False, rate_mult=None, rate_mult_row=None, tprog=None,
+                  tprog_row=None):
         """Integrate N reactors 0 -> tf. With trace_cap > 0 also returns the per-step rows
         trace[N, trace_cap+1, 2n+4] = (t, h, q, p_last, u[n], y_last[n]): u the accepted state, y_last
         and p_last the state and pressure of the step's last RHS evaluation (save_data semantics).
@@ -218,15 +224,21 @@ class Engine:
         rate_mult [nmult, nrg + nrs] scales the net rate of reaction r of reactor i by
         rate_mult[row(i), r] (gas reactions in mechanism order, then surface reactions; forward and
         reverse together; 0 switches a reaction off); rate_mult_row [N] gives the rows, None = one row
-        per reactor."""
+        per reactor.
+        tprog: a prescribed temperature programme T(t) (tprog.TemperatureProgram: one for all reactors, a
+        sequence -- one per reactor, or the rows tprog_row [N] selects -- or a pair (t, T) of [nrows, nk]
+        knot arrays). T is then not read (None is fine), u0 is the caller's state at T(0), and the run
+        uses the wavefront engine."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
         mult, mrow = self._mult(rate_mult, rate_mult_row, N)
+        prog = _tprog.table(tprog, tprog_row, N)
         to, _ = output_grid(tout, N)
-        T, A, tf = self._arr(T, N), self._arr(Asv, N), self._arr(tf, N)
+        T = None if (T is None and prog[0] is not None) else self._arr(T, N)
+        A, tf = self._arr(Asv, N), self._arr(tf, N)
         st = np.zeros((N, _lib.NSTAT))
         yo = None if to is None else np.zeros((N, to.shape[-1], self.n))
-        o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian, mult, mrow)
+        o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian, mult, mrow, prog)
         L = _lib.lib()
         if trace_cap > 0:
             tr = np.zeros((N, trace_cap + 1, 2 * self.n + 4))
@@ -243,13 +255,25 @@ class Engine:
 
     def integrate_device(self, T_ptr, Asv_ptr, u_ptr, tf_ptr, stats_ptr, N, stream_ptr=None, rtol=1e-6,
                          atol=1e-10, max_steps=100000, tout_ptr=None, yout_ptr=None, nout=0, tout_per_reactor=False,
-                         dq_jacobian=False, rate_mult=None, rate_mult_row=None, nmult=0):
+                         dq_jacobian=False, rate_mult=None, rate_mult_row=None, nmult=0, tprog_t=None, tprog_T=None,
+                         ntprog=0, ntprog_rows=0, tprog_row=None):
         """Device-resident variant: raw device pointers (e.g. torch tensor data_ptr()). Dense output
         with tout_ptr / yout_ptr / nout: device arrays tout [nout], or [N, nout] with tout_per_reactor
         (e.g. what phase_tout_device built), and yout [N, nout, n]. Rate multipliers: rate_mult is the
         device pointer of a float64 [nmult, nrg + nrs] table, rate_mult_row that of int32 [N] row indices
-        (None: nmult == N, row i); the library trusts the device arrays."""
+        (None: nmult == N, row i); the library trusts the device arrays. Temperature programmes: tprog_t /
+        tprog_T the device pointers of float64 [ntprog_rows, ntprog] knot arrays, tprog_row that of int32 [N]
+        (None: ntprog_rows == N); T_ptr is then not read."""
         o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        if tprog_t or tprog_T:
+            if not (tprog_t and tprog_T) or ntprog < 1 or ntprog_rows < 1 or (not tprog_row and ntprog_rows != N):
+                raise ValueError(f"tprog needs tprog_t, tprog_T, ntprog >= 1, ntprog_rows >= 1, and ntprog_rows == N = {N} "
+                                 f"without tprog_row; got ntprog = {ntprog}, ntprog_rows = {ntprog_rows}")
+            o.ntprog, o.ntprog_rows = int(ntprog), int(ntprog_rows)
+            o.tprog_t, o.tprog_T = C.cast(C.c_void_p(tprog_t), _lib.dp), C.cast(C.c_void_p(tprog_T), _lib.dp)
+            o.tprog_row = C.cast(C.c_void_p(tprog_row), _lib.ip) if tprog_row else None
+        elif tprog_row:
+            raise ValueError("tprog_row without tprog_t / tprog_T")
         if rate_mult:
             if nmult < 1 or (not rate_mult_row and nmult != N):
                 raise ValueError(f"rate_mult needs nmult >= 1, and nmult == N = {N} without rate_mult_row; got {nmult}")
@@ -266,24 +290,26 @@ class Engine:
                                                C.c_void_p(stats_ptr), C.c_void_p(stream_ptr or 0)))
 
     def integrate_phase(self, T, Asv, u0, tf, tau, rtol=1e-6, atol=1e-10, max_steps=100000, dq_jacobian=False,
-                        rate_mult=None, rate_mult_row=None):
+                        rate_mult=None, rate_mult_row=None, tprog=None, tprog_row=None):
         """Ignition-phase sampling (br_integrate_phase): the states at t = tau[j] * t_ign[i], two passes
         on the device from the same u0 (t_ign, then the outputs at the grid br_phase_tout_dev builds).
         Returns (u, stats) as integrate, with stats["tout"] [N, ntau] (phase_grid(t_ign, tau, tf): NaN
         where t_ign is unknown or the phase is past tf) and stats["yout"] [N, ntau, n] (rows of NaN
-        entries stay 0). Needs the ignition marker species in the mechanism. rate_mult / rate_mult_row as
-        integrate: both passes run with them."""
+        entries stay 0). Needs the ignition marker species in the mechanism. rate_mult / rate_mult_row and
+        tprog / tprog_row as integrate: both passes run with them."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
         mult, mrow = self._mult(rate_mult, rate_mult_row, N)
+        prog = _tprog.table(tprog, tprog_row, N)
         tau = np.ascontiguousarray(np.atleast_1d(tau), dtype=np.float64)
         if tau.ndim != 1 or tau.size == 0:
             raise ValueError(f"tau must be a non-empty 1-D array, got shape {tau.shape}")
-        T, A, tf = self._arr(T, N), self._arr(Asv, N), self._arr(tf, N)
+        T = None if (T is None and prog[0] is not None) else self._arr(T, N)
+        A, tf = self._arr(Asv, N), self._arr(tf, N)
         st = np.zeros((N, _lib.NSTAT))
         to = np.zeros((N, tau.size))
         yo = np.zeros((N, tau.size, self.n))
-        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, mult=mult, mult_row=mrow)
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, mult=mult, mult_row=mrow, prog=prog)
         _lib.check(_lib.lib().br_integrate_phase(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),
                                                  C.byref(o), _lib.dptr(st), tau.size, _lib.dptr(tau), _lib.dptr(to),
                                                  _lib.dptr(yo)))
@@ -292,7 +318,7 @@ class Engine:
         return u, stats
 
     def sensitivity(self, T, Asv, u0, tf, factor=2.0, reactions=None, states=False, rtol=1e-6, atol=1e-10,
-                    max_steps=100000, dq_jacobian=False):
+                    max_steps=100000, dq_jacobian=False, tprog=None, tprog_row=None):
         """Brute-force logarithmic sensitivities to the rate constants (br_sensitivity), built and reduced
         on the device: every base reactor is integrated with each selected reaction's rate times and
         over `factor`. reactions: 0-based indices (gas reactions in mechanism order, then surface
@@ -302,9 +328,11 @@ class Engine:
           "S_u" [N, nsel, n] (with states=True): d u_k(tf) / d ln k_r,
           "u" [N, n] and "stats": the unperturbed end states and stats, as integrate's,
           "nbad": entries set to NaN (a perturbed run failed, or has no t_ign),
-          "reactions": the indices used."""
+          "reactions": the indices used.
+        tprog: not supported here (the library answers BR_ERR_UNSUPPORTED)."""
         u0 = np.ascontiguousarray(np.atleast_2d(u0), dtype=np.float64)
         N = u0.shape[0]
+        prog = _tprog.table(tprog, tprog_row, N)
         if not (np.isfinite(factor) and factor > 1.0):
             raise ValueError(f"factor must be finite and > 1, got {factor}")
         if reactions is None:
@@ -323,7 +351,7 @@ class Engine:
         u = np.zeros((N, self.n))
         st = np.zeros((N, _lib.NSTAT))
         nbad = C.c_longlong(0)
-        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, prog=prog)
         _lib.check(_lib.lib().br_sensitivity(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u0), _lib.dptr(tf),
                                              C.byref(o), float(factor), nsel, _lib.iptr(rx), _lib.dptr(St),
                                              _lib.dptr(Su), _lib.dptr(u), _lib.dptr(st), C.byref(nbad)))
@@ -366,20 +394,23 @@ class Engine:
 
 
 def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, tout=None, rate_mult=None,
-                    rate_mult_row=None):
+                    rate_mult_row=None, tprog=None, tprog_row=None):
     """br_integrate_multi: the ensemble split into contiguous slices over `engines` (one Engine per
     GPU, same mechanism), integrated concurrently; returns (u, stats) in ensemble order. tout as
     Engine.integrate: [nout], or [N, nout] for per-reactor grids (sliced with the ensemble). rate_mult /
-    rate_mult_row as Engine.integrate (the row indices, or the rows of a dense table, are sliced too)."""
+    rate_mult_row and tprog / tprog_row as Engine.integrate (the row indices, or the rows of a dense table,
+    are sliced too)."""
     e0 = engines[0]
     u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
     N = u.shape[0]
     mult, mrow = e0._mult(rate_mult, rate_mult_row, N)
+    prog = _tprog.table(tprog, tprog_row, N)
     to, _ = output_grid(tout, N)
-    T, A, tf = e0._arr(T, N), e0._arr(Asv, N), e0._arr(tf, N)
+    T = None if (T is None and prog[0] is not None) else e0._arr(T, N)
+    A, tf = e0._arr(Asv, N), e0._arr(tf, N)
     st = np.zeros((N, _lib.NSTAT))
     yo = None if to is None else np.zeros((N, to.shape[-1], e0.n))
-    o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo, mult=mult, mult_row=mrow)
+    o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo, mult=mult, mult_row=mrow, prog=prog)
     L = _lib.lib()
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     _lib.check(L.br_integrate_multi(hs, len(engines), N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),

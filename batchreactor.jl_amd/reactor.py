@@ -16,6 +16,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import tprog as _tprog
 from .engine import Engine
 from .mechanism import CONV_REFERENCE, Mechanism, read_batch_xml
 
@@ -268,23 +269,28 @@ def batch_reactor_programmatic(inlet_comp, T, p, time, *, Asv=1.0, chem: Chemist
 
 
 def batch_reactor_ensemble(mech: Mechanism, T, p, X, time, *, Asv=1.0, theta0=None, device=0, rtol=1e-6,
-                           atol=1e-10, tout=None, phase=None):
+                           atol=1e-10, tout=None, phase=None, tprog=None, tprog_row=None):
     """N independent reactors in one call. X: [N, ng] inlet mole fractions. Returns
     (x_end [N, ng], theta_end [N, ns], stats dict of [N] arrays, including t_ign, and "yout"
     [N, nout, n] when output times are given). tout: one grid [nout] for all reactors, or [N, nout],
     row i reactor i's own grid (NaN = no output, trailing only). phase=tau samples every reactor at
     the ignition phases t = tau[j] * t_ign[i] instead (Engine.integrate_phase: stats["tout"] is the grid
-    [N, ntau], NaN where t_ign is unknown or the phase is past `time`)."""
+    [N, ntau], NaN where t_ign is unknown or the phase is past `time`). tprog / tprog_row: prescribed
+    temperature programmes T(t) as Engine.integrate takes them; T is then ignored and every reactor's
+    initial state is built at its programme's T(0)."""
     if phase is not None and tout is not None:
         raise ValueError("give tout or phase, not both")
     X = np.atleast_2d(np.asarray(X, float))
     N = X.shape[0]
     T = np.broadcast_to(np.asarray(T, float), (N,))
+    if tprog is not None:   # T(0) of each reactor's row
+        kt, kT, rows = _tprog.table(tprog, tprog_row, N)
+        T = kT[np.arange(N) if rows is None else rows, 0]
     p = np.broadcast_to(np.asarray(p, float), (N,))
     U0 = np.stack([mech.initial_state(T[i], p[i], X[i], theta0) for i in range(N)]) if N else np.zeros((0, mech.n))
     A, tf = np.broadcast_to(np.asarray(Asv, float), (N,)), np.broadcast_to(np.asarray(time, float), (N,))
     if phase is not None:
-        u, st = _engine(mech, device).integrate_phase(T, A, U0, tf, phase, rtol, atol)
+        u, st = _engine(mech, device).integrate_phase(T, A, U0, tf, phase, rtol, atol, tprog=tprog, tprog_row=tprog_row)
     else:
-        u, st = _engine(mech, device).integrate(T, A, U0, tf, rtol, atol, tout=tout)
+        u, st = _engine(mech, device).integrate(T, A, U0, tf, rtol, atol, tout=tout, tprog=tprog, tprog_row=tprog_row)
     return mech.state_to_molefrac(u), u[:, mech.ng:], st

@@ -107,6 +107,36 @@ typedef struct br_opts {
     double* yout;             /* [N][nout][n] states at tout (host memory for br_integrate,
                                  device memory for br_integrate_dev); rows with tout > tf are
                                  left untouched                                             */
+    int ntprog;               /* knots per temperature programme; 0 (default) = none: every reactor stays
+                                 at its T[i]. With a programme, reactor i's temperature at time t is the
+                                 piecewise-linear interpolant of its row of knots (t_j, T_j),
+                                     T(t) = T_j + (t - t_j) * ((T_{j+1} - T_j) / (t_{j+1} - t_j))
+                                 for t_j <= t < t_{j+1} (this formula, in this order of operations, on
+                                 host and device), held at the last knot's value for t beyond it. The T
+                                 argument of the entry point is then not read and may be NULL; the caller
+                                 builds u0 at T(0). Everything the right-hand side takes from T follows
+                                 T(t): RT in the diagnosed pressure, the coverage factor, every T-only
+                                 constant (with the reactor's rate multipliers). Each RHS is evaluated at
+                                 the time CVODE hands to f; the Jacobian stays d f / d u at that T. A
+                                 programme run always uses the wavefront engine (as traced runs do). The
+                                 BDF is not restarted at a knot: a kink is left to the error test, as
+                                 CVODE does without a tstop there. br_sensitivity with a programme
+                                 returns BR_ERR_UNSUPPORTED; br_rates, br_rhs, br_jacobian take none   */
+    const double* tprog_t;    /* [ntprog_rows][ntprog] knot times, ascending, tprog_t[r][0] == 0; NaN only
+                                 as trailing padding of a row (ragged rows, as in tout)               */
+    const double* tprog_T;    /* [ntprog_rows][ntprog] temperatures [K] at the knots, finite and > 0
+                                 (entries under a NaN time are not read)                              */
+    int ntprog_rows;          /* rows of tprog_t / tprog_T                                            */
+    const int* tprog_row;     /* [N] row of reactor i, or NULL: then ntprog_rows == N and row i (the
+                                 indirection of rate_mult_row: one ramp can serve a whole ensemble).
+                                 Host memory for br_integrate, _traced, _multi (sliced with the
+                                 ensemble) and _phase: every row and row index is checked before any
+                                 launch, BR_ERR_INPUT names the first bad reactor and row. Device
+                                 memory for br_integrate_dev, which checks the shape only. (These five
+                                 sit between yout and dq_jacobian: the fields from dq_jacobian to
+                                 tout_per_reactor stay the struct's tail, in their order; a caller built
+                                 against the earlier header must be rebuilt, and br_version() 220 tells
+                                 the layouts apart)                                                   */
     int dq_jacobian;          /* 1: CVODE's dense difference-quotient Jacobian (cvLsDenseDQJac:
                                  the reference's CVODE_BDF() setting, src/BatchReactor.jl:140,
                                  :204), n extra RHS per Jacobian, in every engine (lane,
@@ -314,12 +344,20 @@ int br_debug_group_eval(br_mech* m, int N, const double* T, const double* Asv, c
 int br_debug_group_lu_solve(int gl, int nm, int N, int n, const double* J, const double* gamma, const double* b,
                             double* x, int* fail, int* perm);
 
+/* temperature-programme check (tests): Tout[i][k] = T(t[i][k]) of reactor i's programme, through the
+ * device evaluator the integrator calls (one thread per reactor; consecutive times of a row reuse the
+ * cached segment, so ascending and descending sequences both exercise the scan). Host arrays; the
+ * programme arguments as the br_opts fields of the same names and checked the same way. */
+int br_debug_tprog_eval(int N, int ntprog, const double* tprog_t, const double* tprog_T, int nrows, const int* tprog_row,
+                        int nt, const double* t /*[N][nt]*/, double* Tout /*[N][nt]*/);
+
 /* User-defined chemistry: replaces solve(ODEProblem(residual!, u0, (0, tf), params), CVODE_BDF();
  * reltol, abstol, save_everystep=false, callback=FunctionCallingCallback(save_data)) with the userchem
  * residual! (src/BatchReactor.jl:51-54,:197-200,:204-210,:358-360,:371-372). The user's RHS is host
  * code (a Julia or Python function: it cannot run in a kernel), so this runs on the CPU: the same
  * CVODE 5.x restatement as the engine, with CVODE's DQ Jacobian (the reference supplies none).
- * f(user, t, u, du) returns 0 (non-zero ends the solve with BR_ERR_RHS); cb(cb_user, t, u) after every
+ * f(user, t, u, du) returns 0 (non-zero ends the solve with BR_ERR_RHS); t is the time CVODE evaluates f
+ * at (tn + hg inside the initial-step estimate, the advanced tn in a step); cb(cb_user, t, u) after every
  * accepted step and at t = 0 and t = tf (save_data's rows). u: u0 in, u(tf) out (the last accepted
  * state on failure); stats[BR_NSTAT] as br_stats. Returns 0 or a BR_ERR_* status. No GPU. */
 typedef int (*br_rhs_fn)(void* user, double t, const double* u, double* du);

@@ -53,12 +53,29 @@ struct BrOpts
     nout::Cint
     tout::Ptr{Float64}          # [nout] ascending output times ([nout x N] with tout_per_reactor)
     yout::Ptr{Float64}          # [N][nout][n]
+    ntprog::Cint                # knots per temperature programme T(t); 0 = none (every reactor at its T)
+    tprog_t::Ptr{Float64}       # [ntprog x ntprog_rows]: column r the ascending knot times of row r, first 0, NaN = trailing padding
+    tprog_T::Ptr{Float64}       # [ntprog x ntprog_rows]: the temperatures [K] at the knots
+    ntprog_rows::Cint
+    tprog_row::Ptr{Cint}        # [N] 0-based row of reactor i, or C_NULL: ntprog_rows == N, row i
     dq_jacobian::Cint           # 1: CVODE's DQ Jacobian (cvLsDenseDQJac, the reference's setting), every engine
     nmult::Cint                 # rows of rate_mult; 0 = no multipliers
     rate_mult::Ptr{Float64}     # [nrg+nrs x nmult]: column q the multipliers of row q, gas reactions in mechanism order, then surface
     rate_mult_row::Ptr{Cint}    # [N] 0-based row of reactor i, or C_NULL: nmult == N, row i
     tout_per_reactor::Cint      # 1: tout is [nout x N], column i reactor i's own ascending grid (NaN = no output, trailing only)
 end
+# The sixteen options without a temperature programme, in the struct's order: the positional form callers
+# had before the programme fields went in between yout and dq_jacobian
+BrOpts(rtol, atol, max_steps, device, hmax, trace_cap, unstable_factor, ignition_species, nout, tout, yout,
+       dq_jacobian, nmult, rate_mult, rate_mult_row, tout_per_reactor) =
+    BrOpts(rtol, atol, max_steps, device, hmax, trace_cap, unstable_factor, ignition_species, nout, tout, yout,
+           Cint(0), C_NULL, C_NULL, Cint(0), C_NULL, dq_jacobian, nmult, rate_mult, rate_mult_row, tout_per_reactor)
+# a copy of `o` with the named fields replaced
+set_fields(o::BrOpts; kw...) =
+    BrOpts((haskey(kw, f) ? kw[f] : getfield(o, f) for f in fieldnames(BrOpts))...)
+# `o` with the temperature programme of `from`
+keep_tprog(o::BrOpts, from::BrOpts) = set_fields(o; ntprog=from.ntprog, tprog_t=from.tprog_t, tprog_T=from.tprog_T,
+                                                 ntprog_rows=from.ntprog_rows, tprog_row=from.tprog_row)
 # dq_jacobian=true selects CVODE's difference-quotient Jacobian, the reference's CVODE_BDF() setting
 # (src/BatchReactor.jl:140,:204); the default is the analytic Jacobian
 BrOpts(; rtol=1e-6, atol=1e-10, max_steps=100_000, device=0, hmax=0.0, unstable_factor=0.0, ignition_species=0,
@@ -69,10 +86,21 @@ BrOpts(; rtol=1e-6, atol=1e-10, max_steps=100_000, device=0, hmax=0.0, unstable_
 # the same options with a rate-multiplier table (br_opts.rate_mult): `mult` is (nrg+nrs) x nmult, `rows` the
 # 0-based row of every reactor or nothing (one column per reactor). The caller keeps both arrays alive
 # (GC.@preserve) for the call that takes the options.
-with_rate_mult(o::BrOpts, mult::Matrix{Float64}, rows::Union{Nothing,Vector{Cint}}=nothing) =
-    BrOpts(o.rtol, o.atol, o.max_steps, o.device, o.hmax, o.trace_cap, o.unstable_factor, o.ignition_species,
-           o.nout, o.tout, o.yout, o.dq_jacobian, Cint(size(mult, 2)), pointer(mult),
-           rows === nothing ? Ptr{Cint}(C_NULL) : pointer(rows), o.tout_per_reactor)
+function with_rate_mult(o::BrOpts, mult::Matrix{Float64}, rows::Union{Nothing,Vector{Cint}}=nothing)
+    r = BrOpts(o.rtol, o.atol, o.max_steps, o.device, o.hmax, o.trace_cap, o.unstable_factor, o.ignition_species,
+               o.nout, o.tout, o.yout, o.dq_jacobian, Cint(size(mult, 2)), pointer(mult),
+               rows === nothing ? Ptr{Cint}(C_NULL) : pointer(rows), o.tout_per_reactor)
+    return keep_tprog(r, o)
+end
+# the same options with temperature programmes T(t) (br_opts.ntprog): `t` and `Tk` are ntprog x nrows, column r
+# the knots of row r (times ascending from 0, NaN = trailing padding; T piecewise linear between the knots,
+# held beyond the last); `rows` the 0-based row of every reactor or nothing (one column per reactor). The T
+# argument of the integrate call is then not read. The caller keeps the arrays alive (GC.@preserve).
+function with_tprog(o::BrOpts, t::Matrix{Float64}, Tk::Matrix{Float64}, rows::Union{Nothing,Vector{Cint}}=nothing)
+    size(t) == size(Tk) || error("tprog: t and T must have the same size")
+    return set_fields(o; ntprog=Cint(size(t, 1)), tprog_t=pointer(t), tprog_T=pointer(Tk), ntprog_rows=Cint(size(t, 2)),
+                      tprog_row=(rows === nothing ? Ptr{Cint}(C_NULL) : pointer(rows)))
+end
 
 # br_stats rows of the [NSTAT x N] matrix returned below
 const STAT_FIELDS = (:nsteps, :nfe, :nje, :nsetups, :nni, :ncfn, :netf, :status, :cyc_total, :cyc_rhs, :cyc_jac,
@@ -111,6 +139,7 @@ function integrate_traced!(m::Ptr{Cvoid}, T, Asv, u::Matrix{Float64}, tf; cap::I
     o = BrOpts(opts.rtol, opts.atol, opts.max_steps, opts.device, opts.hmax, Cint(cap), opts.unstable_factor,
                opts.ignition_species, Cint(0), C_NULL, C_NULL, opts.dq_jacobian,
                opts.nmult, opts.rate_mult, opts.rate_mult_row, Cint(0))
+    o = keep_tprog(o, opts)
     check(ccall((:br_integrate_traced, lib), Cint,
                 (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BrOpts}, Ptr{Float64},
                  Ptr{Float64}), m, N, T, Asv, u, tf, Ref(o), stats, trace))
@@ -433,16 +462,27 @@ end
 end time, in one call (one br_integrate over the ensemble). Returns (x_end [ng x N], theta_end
 [ns x N], stats [NSTAT x N], including t_ign from the OH marker). With `phase=tau` every reactor is
 also sampled at the ignition phases t = tau[j] * t_ign[i] (integrate_phase!) and the call returns
-(x_end, theta_end, stats, tout [ntau x N], yout [n x ntau x N])."""
+(x_end, theta_end, stats, tout [ntau x N], yout [n x ntau x N]).
+`tprog=(t, Tk)` or `(t, Tk, rows)` prescribes temperature programmes T(t) (with_tprog: knot matrices
+ntprog x nrows, `rows` the 0-based row of every reactor or one column per reactor): `T` is then ignored and
+every reactor's initial state is built at its programme's T(0)."""
 function batch_reactor_ensemble(md::DeviceMech, T::AbstractVector, p::AbstractVector, comps::AbstractVector,
-                                tf; Asv=1.0, rtol::Real=1e-6, atol::Real=1e-10, phase=nothing)
+                                tf; Asv=1.0, rtol::Real=1e-6, atol::Real=1e-10, phase=nothing, tprog=nothing)
     N = length(T)
     U = zeros(ncomp(md), N)
+    kt = tprog === nothing ? zeros(0, 0) : Matrix{Float64}(tprog[1])
+    kT = tprog === nothing ? zeros(0, 0) : Matrix{Float64}(tprog[2])
+    krow = (tprog === nothing || length(tprog) < 3 || tprog[3] === nothing) ? nothing : Vector{Cint}(tprog[3])
+    T0(i) = tprog === nothing ? T[i] : kT[1, krow === nothing ? i : krow[i] + 1]
     for i in 1:N
-        U[:, i] = initial_state(md, T[i], p[i], comps[i])
+        U[:, i] = initial_state(md, T0(i), p[i], comps[i])
     end
     fillv(v) = v isa AbstractVector ? collect(Float64, v) : fill(Float64(v), N)
     opts = BrOpts(rtol=rtol, atol=atol, ignition_species=ignition_species(md))
+    if tprog !== nothing
+        opts = with_tprog(opts, kt, kT, krow)
+    end
+    GC.@preserve kt kT krow begin
     if phase !== nothing
         stats, tout, yout = integrate_phase!(md.m, collect(Float64, T), fillv(Asv), U, fillv(tf),
                                              collect(Float64, phase); opts=opts)
@@ -452,6 +492,7 @@ function batch_reactor_ensemble(md::DeviceMech, T::AbstractVector, p::AbstractVe
     stats = integrate!(md.m, collect(Float64, T), fillv(Asv), U, fillv(tf); opts=opts)
     X = reduce(hcat, [state_to_molefrac(md, U[:, i]) for i in 1:N])
     return X, U[md.ng+1:end, :], stats
+    end
 end
 
 """ignition_sensitivity: d ln t_ign / d ln k_r of N reactors (T, p, inlet composition and end time each)
@@ -621,7 +662,7 @@ function batch_reactor(input_file::AbstractString, lib_dir::AbstractString, user
 end
 
 export batch_reactor, batch_reactor_ensemble, compile_mechanism, read_batch_xml, DeviceMech, Chemistry,
-       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!, with_rate_mult, sensitivity,
+       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!, with_rate_mult, with_tprog, sensitivity,
        ignition_sensitivity
 
 end # module
