@@ -1,6 +1,6 @@
-// brhip_debug.hpp -- test and diagnostic kernels (k_lu_check*, k_group_eval, k_group_lu) and their
-// extern "C" entry points (br_debug_*, br_diag_sub). Included at the end of brhip.hip: they use its
-// error helpers and br_mech.
+// brhip_debug.hpp -- test and diagnostic kernels (k_lu_check*, k_group_eval, k_group_lu, k_lane_eval,
+// k_lane_lu, k_wave_eval) and their extern "C" entry points (br_debug_*, br_diag_sub). Included at the
+// end of brhip.hip: they use its error helpers and br_mech.
 // ------------------------------------------------------------------------------------
 // dense-solver check: factor (I - gamma*J) with the row-per-lane LU of the integrator and
 // solve one right-hand side per matrix. J[N][n][n] row-major, b/x [N][n].
@@ -238,6 +238,306 @@ extern "C" int br_debug_group_lu_solve(int gl, int nm, int N, int n, const doubl
     HIPCHK(hipMemcpy(x, dx, (size_t)N * n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(fail_out, df, (size_t)N * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(perm, dp, (size_t)N * n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// rate multipliers of a check's launch (host arrays, checked as br_integrate checks them): the table and the
+// row indices to the device, the launch's half of the MultBlock, and the tag on the launch's g_par
+static int debug_stage_mult(br_mech* m, int N, int nmult, const double* mult, const int* row, DevScratch& S, DevMech& dm) {
+    if (nmult == 0) return 0;
+    br_opts o{};
+    o.nmult = nmult; o.rate_mult = mult; o.rate_mult_row = row;
+    if (const int rc = check_mult_host(m, N, &o)) return rc;
+    const size_t nt = (size_t)nmult * (m->nrg + m->nrs);
+    double* dmult;
+    int* drow = nullptr;
+    HIPCHK(S.alloc(&dmult, std::max<size_t>(nt, 1) * 8));
+    HIPCHK(hipMemcpy(dmult, mult, nt * 8, hipMemcpyHostToDevice));
+    if (row) {
+        HIPCHK(S.alloc(&drow, (size_t)N * 4));
+        HIPCHK(hipMemcpy(drow, row, (size_t)N * 4, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_mult_block, dim3(1), dim3(64), 0, 0, m->mult_hdr, (const double*)dmult, (const int*)drow);
+    HIPCHK(hipGetLastError());
+    dm.g_par = reinterpret_cast<const double*>(reinterpret_cast<size_t>(dm.g_par) | 1u);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// lane-engine checks (tests): the device functions of k_lane (brhip_lane.hpp) on their own, with k_lane's
+// workgroup shape, LDS rows, global rows and buffer resource
+// ------------------------------------------------------------------------------------
+namespace {
+// RHS and analytic Jacobian of reactors lane + 64 (block + k blocks), k = 0, 1, ..., one after another in the
+// lane's LDS rows and global rows: a lane that gets a second reactor (N > 64 blocks) reuses the T-only
+// constants', the concentrations' and the saved-J rows with another T as in k_lane's refill. A lane without a
+// reactor stays masked until the wave is done.
+template <int NM>
+__global__ __launch_bounds__(64) void k_lane_eval(DevMech M, int N, const double* __restrict__ Tv,
+                                                  const double* __restrict__ U, double* __restrict__ DU,
+                                                  double* __restrict__ Jout, double* __restrict__ Jg) {
+    const int lane = threadIdx.x;
+    const int n = MF(n);
+    const LaneLay LL = lane_lay(NM, n, MF(nset), MF(nrg), MF(nfo));
+    double* Lp = reinterpret_cast<double*>(br_lds) + lane;
+    Lp[(LL.conc + n) * 64] = 1.0;
+    GRows G;
+    G.r = __builtin_amdgcn_make_buffer_rsrc(Jg, 0, 0x7fffffff, 0x00020000);
+    G.vo = lane * 8;
+    G.base = blockIdx.x * LL.g_rows * 512;
+    const int stride = 64 * (int)gridDim.x;
+    for (int rid = lane + 64 * (int)blockIdx.x;; rid += stride) {
+        const bool has = rid < N;
+        if (!__any(has)) break;
+        if (has) {
+            lane_tconst(LL, Lp, G, Tv[rid], n, rid);
+            double y[NM], f[NM];
+#pragma unroll
+            for (int i = 0; i < NM; ++i) y[i] = i < n ? U[(size_t)rid * n + i] : 0.0;
+            lane_rhs<NM>(LL, Lp, G, y, n, f);
+#pragma unroll
+            for (int i = 0; i < NM; ++i) if (i < n) DU[(size_t)rid * n + i] = f[i];
+            lane_jac<NM>(LL, Lp, G, n);                                 // (reads the concentrations the RHS left)
+#pragma unroll
+            for (int j = 0; j < NM; ++j)
+#pragma unroll
+                for (int i = 0; i < NM; ++i)                            // the saved-J rows as k_lane's LU setup reads them
+                    if (i < n && j < n) Jout[((size_t)rid * n + i) * n + j] = G.ld(j * NM + i);
+        }
+    }
+}
+
+// l_getrf + l_getrs of matrix i in lane i mod 64 of block i / 64: J through the lane's saved-J rows, I - gamma J
+// in k_lane's expression order, the factors and reciprocal pivots through the g_lu / g_rpv rows. A lane with
+// skip[i] != 0 does nothing (in the integrator only some lanes of a wave set up).
+template <int NM>
+__global__ __launch_bounds__(64) void k_lane_lu(int N, int n, const double* __restrict__ J, const double* __restrict__ g,
+                                                const double* __restrict__ b, const int* __restrict__ skip,
+                                                double* __restrict__ x, int* __restrict__ fail_out, int* __restrict__ piv,
+                                                double* __restrict__ Jg) {
+    const int lane = threadIdx.x;
+    const int i = (int)blockIdx.x * 64 + lane;
+    const LaneLay LL = lane_lay(NM, n, 0, 0, 0);
+    GRows G;
+    G.r = __builtin_amdgcn_make_buffer_rsrc(Jg, 0, 0x7fffffff, 0x00020000);
+    G.vo = lane * 8;
+    G.base = blockIdx.x * LL.g_rows * 512;
+    const bool act = i < N && !(skip && skip[i]);
+    if (act) {
+#pragma unroll
+        for (int c = 0; c < NM; ++c)
+#pragma unroll
+            for (int r = 0; r < NM; ++r)
+                if (r < n && c < n) G.st(c * NM + r, J[((size_t)i * n + r) * n + c]);
+        const double mg = -g[i];
+        double a[NM][NM], rpv[NM], rhs_[NM];
+        unsigned long long pv = 0;
+#pragma unroll
+        for (int c = 0; c < NM; ++c)
+#pragma unroll
+            for (int r = 0; r < NM; ++r) a[r][c] = (r < n && c < n) ? G.ld(c * NM + r) : 0.0;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < NM; ++c)
+#pragma unroll
+            for (int r = 0; r < NM; ++r) a[r][c] = a[r][c] * mg + (r == c ? 1.0 : 0.0);
+        const int f = l_getrf<NM>(a, pv, rpv);
+#pragma unroll
+        for (int c = 0; c < NM; ++c) {
+            G.st(LL.g_rpv + c, rpv[c]);
+#pragma unroll
+            for (int r = 0; r < NM; ++r) G.st(LL.g_lu + c * NM + r, a[r][c]);
+        }
+#pragma unroll
+        for (int r = 0; r < NM; ++r) rhs_[r] = r < n ? b[(size_t)i * n + r] : 0.0;
+        if (!f) l_getrs<NM>(G, LL, pv, rhs_);                           // (k_lane: no solve after a zero pivot)
+#pragma unroll
+        for (int r = 0; r < NM; ++r)
+            if (r < n) {
+                x[(size_t)i * n + r] = f ? 0.0 : rhs_[r];
+                piv[(size_t)i * n + r] = (int)((pv >> (4 * r)) & 15);
+            }
+        fail_out[i] = f;
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// wavefront-engine check (tests): init_tconst<CPL, true>, rhs and jacobian in the integrator's configuration
+// (wave_ctx<CPL, NMAX>, rpb waves per workgroup on one table block, the per-slot workspace of k_integrate)
+// ------------------------------------------------------------------------------------
+// RHS and analytic Jacobian of reactors slot, slot + G, slot + 2G, ... (G = waves of the grid), one after
+// another in the wave's LDS block and workspace slot. With Tprev: the constants are first built at Tprev[rid]
+// and used by one discarded RHS, then rebuilt at T[rid] in the live slot by the refresh sequence of
+// k_integrate's temperature-programme instances (wave_sync, init_tconst) before the evaluation.
+template <int NMAX>
+__global__ __launch_bounds__(64 * br_maxrpb(NMAX)) void k_wave_eval(DevMech M, int N, int rpb, const double* __restrict__ Tv,
+                                                                    const double* __restrict__ Asvv,
+                                                                    const double* __restrict__ U,
+                                                                    const double* __restrict__ Tprev,
+                                                                    double* __restrict__ DU, double* __restrict__ Jout,
+                                                                    double* __restrict__ Jws) {
+    constexpr int CPL = NMAX > 64 ? 2 : 1;
+    constexpr int JW = NMAX > 64 ? CR2 : 64;                            // column stride of the saved J (col_rows)
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const WaveCtx W = wave_ctx<CPL, NMAX>(M, smem_raw, rpb, Jws);
+    const int widx = W.rid;                                             // workspace slot of this wave
+    const int G = (int)gridDim.x * rpb;
+    const int lane = W.lane;
+    const Tab& tb = W.tb;
+    const RView& S = W.R;
+    const int n = M.n;
+    double* Jsave = Jws + (size_t)widx * ws_doubles(NMAX, M.nrg);       // as k_integrate lays its slot out
+    double* jscr = Jsave + NMAX * col_rows(NMAX);
+    double* p_last = reinterpret_cast<double*>(W.rbase);
+    const int legs = Tprev ? 2 : 1;
+    for (int rid = widx; rid < N; rid += G) {
+        wave_sync();
+        const double Asv = Asvv ? Asvv[rid] : 1.0;
+        const double Asv_th = (M.conv & 4) ? 1.0 : Asv;
+        double u[CPL], du[CPL];
+#pragma unroll
+        FOR_S u[s] = CS < n ? U[(size_t)rid * n + CS] : 0.0;
+        double T = 0.0;
+#pragma unroll 1
+        for (int leg = 0; leg < legs; ++leg) {                          // (one copy of init_tconst and rhs)
+            T = uni(leg == legs - 1 ? Tv[rid] : Tprev[rid]);
+            if (leg) wave_sync();                                       // tprog_refresh
+            init_tconst<CPL, true>(M, tb, S, T, lane, rid);
+            rhs<CPL>(M, tb, S, T, Asv, Asv_th, u, lane, p_last, du);    // (leg 0 of 2: discarded)
+        }
+#pragma unroll
+        FOR_S if (CS < n) DU[(size_t)rid * n + CS] = du[s];
+        jacobian<CPL>(M, tb, S, T, Asv, Asv_th, u, lane, Jsave, jscr);
+        // the saved J as lu_factor / lu_factor2 read it: a buffer of n columns of JW rows, row per lane
+        const __amdgpu_buffer_rsrc_t rj =
+            __builtin_amdgcn_make_buffer_rsrc((void*)launder(Jsave), (short)0, n * (JW * 8), 0x00020000);
+#pragma unroll
+        FOR_S {
+            if (CS < n) {
+                double* row = Jout + ((size_t)rid * n + CS) * n;
+                for (int j = 0; j < n; ++j)
+                    row[j] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rj, (unsigned)CS * 8u, j * (JW * 8), 0));
+            }
+        }
+    }
+}
+}  // namespace
+
+static const void* lane_eval_kernel(int nm) {
+    return nm == 9 ? (const void*)k_lane_eval<9> : nm == 12 ? (const void*)k_lane_eval<12> : nullptr;
+}
+static const void* lane_lu_kernel(int nm) {
+    return nm == 9 ? (const void*)k_lane_lu<9> : nm == 12 ? (const void*)k_lane_lu<12> : nullptr;
+}
+static const void* wave_eval_kernel(int nmax) {
+    return nmax == 16 ? (const void*)k_wave_eval<16> : nmax == 32 ? (const void*)k_wave_eval<32>
+         : nmax == 56 ? (const void*)k_wave_eval<56> : nmax == 64 ? (const void*)k_wave_eval<64>
+         : nmax == 72 ? (const void*)k_wave_eval<72> : nullptr;
+}
+
+extern "C" int br_debug_lane_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
+                                  const int* rate_mult_row, double* du, double* J) {
+    if (!m || N <= 0 || !T || !u || !du || !J) return fail(BR_ERR_INPUT, "bad argument");
+    if (!m->lane_nm) return fail(BR_ERR_UNSUPPORTED, "mechanism is not eligible for the lane engine");
+    HIPCHK(hipSetDevice(m->device));
+    const int n = m->n, NM = m->lane_nm;
+    // small fixed grid: one workgroup up to 128 reactors, else two, so that lanes take a second reactor in
+    // the rows of their first from N = 65 on (N = 100: lanes 0..35 of the one workgroup; N >= 192: every lane)
+    const int blocks = std::min(2, (N + 127) / 128);
+    const size_t rows = (size_t)lane_lay(NM, n, m->dm.nset, m->nrg, m->dm.nfo).g_rows;
+    double *dT, *du_, *ddu, *dJ, *dws;
+    DevScratch S;
+    DevMech dm = m->dm;
+    if (const int rc = debug_stage_mult(m, N, nmult, rate_mult, rate_mult_row, S, dm)) return rc;
+    HIPCHK(S.alloc(&dT, (size_t)N * 8));
+    HIPCHK(S.alloc(&du_, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&ddu, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&dJ, (size_t)N * n * n * 8));
+    HIPCHK(S.alloc(&dws, rows * blocks * 64 * 8));
+    HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
+    const void* fn = lane_eval_kernel(NM);
+    if (!fn) return fail(BR_ERR_UNSUPPORTED, "no lane check kernel of this width");
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lane_shmem));
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dJ, (void*)&dws};
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64), args, m->lane_shmem, 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(du, ddu, (size_t)N * n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(J, dJ, (size_t)N * n * n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int br_debug_lane_lu_solve(int nm, int N, int n, const double* J, const double* gamma, const double* b,
+                                      const int* skip, double* x, int* fail_out, int* piv) {
+    const void* fn = lane_lu_kernel(nm);
+    if (!fn || N <= 0 || n < 1 || n > nm || !J || !gamma || !b || !x || !fail_out || !piv) return fail_code_input();
+    const int blocks = (N + 63) / 64;
+    const size_t rows = (size_t)lane_lay(nm, n, 0, 0, 0).g_rows;
+    double *dJ, *dg, *db, *dx, *dws;
+    int *df, *dp, *dsk = nullptr;
+    DevScratch S;
+    HIPCHK(S.alloc(&dJ, (size_t)N * n * n * 8));
+    HIPCHK(S.alloc(&dg, (size_t)N * 8));
+    HIPCHK(S.alloc(&db, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&dx, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&dws, rows * blocks * 64 * 8));
+    HIPCHK(S.alloc(&df, (size_t)N * 4));
+    HIPCHK(S.alloc(&dp, (size_t)N * n * 4));
+    HIPCHK(hipMemcpy(dJ, J, (size_t)N * n * n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dg, gamma, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, b, (size_t)N * n * 8, hipMemcpyHostToDevice));
+    // (the outputs start from the caller's values: a skipped lane writes none)
+    HIPCHK(hipMemcpy(dx, x, (size_t)N * n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(df, fail_out, (size_t)N * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dp, piv, (size_t)N * n * 4, hipMemcpyHostToDevice));
+    if (skip) {
+        HIPCHK(S.alloc(&dsk, (size_t)N * 4));
+        HIPCHK(hipMemcpy(dsk, skip, (size_t)N * 4, hipMemcpyHostToDevice));
+    }
+    void* args[] = {(void*)&N, (void*)&n, (void*)&dJ, (void*)&dg, (void*)&db, (void*)&dsk, (void*)&dx, (void*)&df, (void*)&dp,
+                    (void*)&dws};
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64), args, 0, 0));
+    HIPCHK(hipMemcpy(x, dx, (size_t)N * n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(fail_out, df, (size_t)N * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(piv, dp, (size_t)N * n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int br_debug_wave_eval(br_mech* m, int N, const double* T, const double* Asv, const double* u, const double* T_prev,
+                                  int nmult, const double* rate_mult, const int* rate_mult_row, double* du, double* J) {
+    if (!m || N <= 0 || !T || !u || !du || !J) return fail(BR_ERR_INPUT, "bad argument");
+    HIPCHK(hipSetDevice(m->device));
+    const int n = m->n, rpb = m->rpb;
+    // small fixed grid: one workgroup up to 4 rpb reactors, else two, so that every wave takes a second
+    // reactor in the slot of its first from N = 2 rpb (one workgroup) or 4 rpb (two) on
+    const int blocks = std::min(2, (N + 4 * rpb - 1) / (4 * rpb));
+    double *dT, *dA, *du_, *dTp = nullptr, *ddu, *dJ, *dws;
+    DevScratch S;
+    DevMech dm = m->dm;
+    if (const int rc = debug_stage_mult(m, N, nmult, rate_mult, rate_mult_row, S, dm)) return rc;
+    HIPCHK(S.alloc(&dT, (size_t)N * 8));
+    HIPCHK(S.alloc(&dA, (size_t)N * 8));
+    HIPCHK(S.alloc(&du_, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&ddu, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&dJ, (size_t)N * n * n * 8));
+    HIPCHK(S.alloc(&dws, (size_t)blocks * rpb * ws_doubles(m->nmax, m->nrg) * 8));
+    HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
+    if (Asv) HIPCHK(hipMemcpy(dA, Asv, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
+    if (T_prev) {
+        HIPCHK(S.alloc(&dTp, (size_t)N * 8));
+        HIPCHK(hipMemcpy(dTp, T_prev, (size_t)N * 8, hipMemcpyHostToDevice));
+    }
+    const void* fn = wave_eval_kernel(m->nmax);
+    if (!fn) return fail(BR_ERR_UNSUPPORTED, "no wavefront check kernel of this width");
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->shmem));
+    const double* pA = Asv ? dA : nullptr;
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&pA, (void*)&du_, (void*)&dTp, (void*)&ddu, (void*)&dJ,
+                    (void*)&dws};
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->shmem, 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(du, ddu, (size_t)N * n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(J, dJ, (size_t)N * n * n * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

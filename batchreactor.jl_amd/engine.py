@@ -189,6 +189,52 @@ class Engine:
                                                   _lib.dptr(J)))
         return du, J
 
+    def lane_eval(self, T, u, rate_mult=None, rate_mult_row=None):
+        """(du, J) as the lane integrator of this mechanism evaluates them (br_debug_lane_eval: lane_tconst,
+        lane_rhs, lane_jac in k_lane's LDS rows and global rows); rate_mult / rate_mult_row as integrate"""
+        u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
+        N = u.shape[0]
+        T = self._arr(T, N)
+        mult, mrow = self._mult(rate_mult, rate_mult_row, N)
+        du = np.zeros_like(u)
+        J = np.zeros((N, self.n, self.n))
+        _lib.check(_lib.lib().br_debug_lane_eval(self.h, N, _lib.dptr(T), _lib.dptr(u), 0 if mult is None else mult.shape[0],
+                                                 _lib.dptr(mult), _lib.iptr(mrow), _lib.dptr(du), _lib.dptr(J)))
+        return du, J
+
+    @staticmethod
+    def lane_lu(nm, J, gamma, b, skip=None, fill=-7.0):
+        """(x, fail, piv) of the lane integrator's register LU and solve, k_lane<nm> (br_debug_lane_lu_solve):
+        x [N, n], fail [N], piv [N, n] the pivot row of each step. skip [N]: matrices left out; their x
+        entries keep `fill`, their fail and piv entries -1."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        N, n = b.shape
+        J = np.ascontiguousarray(J, dtype=np.float64)
+        g = np.ascontiguousarray(gamma, dtype=np.float64)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32)
+        x = np.full((N, n), fill)
+        f = np.full(N, -1, np.int32)
+        piv = np.full((N, n), -1, np.int32)
+        _lib.check(_lib.lib().br_debug_lane_lu_solve(nm, N, n, _lib.dptr(J), _lib.dptr(g), _lib.dptr(b), _lib.iptr(sk),
+                                                     _lib.dptr(x), _lib.iptr(f), _lib.iptr(piv)))
+        return x, f, piv
+
+    def wave_eval(self, T, Asv, u, T_prev=None, rate_mult=None, rate_mult_row=None):
+        """(du, J) as the wavefront integrator of this mechanism evaluates them (br_debug_wave_eval: k_integrate's
+        instance width, reactors per workgroup, slots and init_tconst). T_prev [N]: the T-only constants are
+        built at T_prev first and refreshed to T in the live slot, as in a temperature-programme run."""
+        u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
+        N = u.shape[0]
+        T, A = self._arr(T, N), self._arr(Asv, N)
+        Tp = None if T_prev is None else self._arr(T_prev, N)
+        mult, mrow = self._mult(rate_mult, rate_mult_row, N)
+        du = np.zeros_like(u)
+        J = np.zeros((N, self.n, self.n))
+        _lib.check(_lib.lib().br_debug_wave_eval(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(Tp),
+                                                 0 if mult is None else mult.shape[0], _lib.dptr(mult), _lib.iptr(mrow),
+                                                 _lib.dptr(du), _lib.dptr(J)))
+        return du, J
+
     def _mult(self, rate_mult, rate_mult_row, N):
         """rate_mult_table for this mechanism's nrg + nrs reactions; (None, None) without multipliers"""
         if rate_mult is None and rate_mult_row is None:

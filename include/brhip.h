@@ -344,6 +344,34 @@ int br_debug_group_eval(br_mech* m, int N, const double* T, const double* Asv, c
 int br_debug_group_lu_solve(int gl, int nm, int N, int n, const double* J, const double* gamma, const double* b,
                             double* x, int* fail, int* perm);
 
+/* lane-engine check (tests): RHS and analytic Jacobian as the one-reactor-per-lane integrator evaluates
+ * them (lane_tconst, lane_rhs, lane_jac in k_lane's workgroup shape, LDS rows and global rows;
+ * BR_ERR_UNSUPPORTED when the mechanism has no lane instance: surface species or n > 12). One workgroup
+ * up to N = 128, two above: a lane evaluates reactors lane + 64 (block + k blocks), k = 0, 1, ..., one after
+ * another in the same rows (N = 100: lanes 0..35 take a second reactor, lanes 36..63 wait masked). nmult, rate_mult,
+ * rate_mult_row: per-reactor rate multipliers as the br_opts fields of the same names (nmult = 0: none).
+ * du[N][n]; J[N][n][n] row-major, as br_jacobian. */
+int br_debug_lane_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
+                       const int* rate_mult_row, double* du, double* J);
+
+/* lane-engine check (tests): the register LU and solve of k_lane<nm>, nm = 9 or 12, 1 <= n <= nm (else
+ * BR_ERR_INPUT). J, gamma, b, x, fail as br_debug_lu_solve; matrix i sits in lane i mod 64 of workgroup
+ * i / 64. piv[N][n]: the pivot row chosen at each step (denseGETRF's p[k]); fail[i] = 0 or (k+1) for a
+ * zero pivot (x_i = 0 then). skip[N] (or NULL): a matrix with skip[i] != 0 is left out, its lane idle, and
+ * its x, fail and piv entries keep the caller's values. */
+int br_debug_lane_lu_solve(int nm, int N, int n, const double* J, const double* gamma, const double* b, const int* skip,
+                           double* x, int* fail, int* piv);
+
+/* wavefront-engine check (tests): RHS and analytic Jacobian as k_integrate evaluates them: the
+ * mechanism's instance width, its reactors per workgroup on one table block, init_tconst with the
+ * multiplier path, the workspace slot layout, J read as the LU reads it. One workgroup up to N = 4 rpb
+ * reactors (rpb: br_mech_launch_info of the wavefront engine), two above: a wave evaluates reactors slot,
+ * slot + waves, ... one after another in the same LDS block and slot. T_prev[N] (or NULL): the
+ * T-only constants are first built at T_prev and used once, then rebuilt at T in the live slot as a
+ * temperature-programme run refreshes them. Multipliers as br_debug_lane_eval. Asv may be NULL (1.0). */
+int br_debug_wave_eval(br_mech* m, int N, const double* T, const double* Asv, const double* u, const double* T_prev,
+                       int nmult, const double* rate_mult, const int* rate_mult_row, double* du, double* J);
+
 /* temperature-programme check (tests): Tout[i][k] = T(t[i][k]) of reactor i's programme, through the
  * device evaluator the integrator calls (one thread per reactor; consecutive times of a row reuse the
  * cached segment, so ascending and descending sequences both exercise the scan). Host arrays; the

@@ -56,6 +56,7 @@ typedef struct {
     int stick, stick_gas;
     double A, b, Ea;                /* SI (arrhenius) or s0 (stick); Ea [J/mol] */
     int ncov, cov_sp[8]; double cov_eps[8];  /* eps [J/mol], cov_sp combined index */
+    double mul;                     /* multiplier on k(T) (1.0; orc_set_rxn_mult, index nrg + i) */
 } srxn_t;
 
 struct orc_mech {
@@ -82,6 +83,7 @@ void orc_initial_coverage(const orc_mech* m, double* th) { for (int i = 0; i < m
 void orc_set_conv(orc_mech* m, int conv) { m->conv = conv; }
 void orc_set_rxn_mult(orc_mech* m, int i, double fmul, double rmul) {
     if (i >= 0 && i < m->nrg) { m->gr[i].fmul = fmul; m->gr[i].rmul = rmul; }
+    else if (i >= m->nrg && i < m->nrg + m->nrs) m->sr[i - m->nrg].mul = fmul;   /* surface: one direction */
 }
 
 /* atomic weights [g/mol]. H/C/O/N fitted to the golden: they reproduce rho0 of
@@ -441,6 +443,7 @@ static int load_surface(orc_mech* m, const char* path) {
             *at = 0;
             if (m->nrs == cap) { cap *= 2; m->sr = (srxn_t*)realloc(m->sr, (size_t)cap * sizeof(srxn_t)); }
             srxn_t* r = &m->sr[m->nrs]; memset(r, 0, sizeof *r);
+            r->mul = 1.0;
             char* arrow = strstr(body, "=>");
             if (!arrow) { seterr("surface rxn without '=>'"); return -1; }
             *arrow = 0;
@@ -575,6 +578,7 @@ static void tcache_init(const orc_mech* m, double T, tcache_t* c) {
         const srxn_t* r = &m->sr[i];
         if (r->stick) c->ks[i] = r->A * sqrt(R_GAS * T / (2 * M_PI * m->M[r->stick_gas]));
         else c->ks[i] = r->A * pow(T, r->b) * exp(-r->Ea / (R_GAS * T));
+        if (r->mul != 1.0) c->ks[i] *= r->mul;
     }
 }
 static void tcache_free(tcache_t* c) { free(c->kf); }

@@ -86,7 +86,8 @@ double orc_molwt(const orc_mech* m, int k);
 double orc_site_density(const orc_mech* m);               /* mol/cm2 */
 void   orc_initial_coverage(const orc_mech* m, double* th);
 void   orc_set_conv(orc_mech* m, int conv);
-/* test hook: multiply gas reaction i's forward / reverse terms (default 1.0) */
+/* test hook: multiply gas reaction i's forward / reverse terms (default 1.0); i = nrg + s: surface
+ * reaction s's k(T) by fmul (one direction, rmul unused) */
 void   orc_set_rxn_mult(orc_mech* m, int i, double fmul, double rmul);
 
 /* rho_k from mole fractions (src/BatchReactor.jl:224-232 / IdealGas.density) */

@@ -299,6 +299,55 @@ def test_generated_falloff_mechanisms(pkg, tmp_path, key, troe3):
     np.testing.assert_array_equal(nat["theta0"], m.theta0)
 
 
+# the lane-eligible falloff mechanisms tests/test_lane_kernels.py generates: n, gas reactions, and the
+# counts of (Lindemann, Troe, +M, irreversible, three-product) reactions in each, and of the reactions with
+# three product slots (l12e: O+CH3=>H+H2+CO, and HCO+H2O<=>H+CO+H2O with H2O on both sides)
+_LANE_SUBSET_CONTENTS = {"l9": (9, 28, 0, 1, 5, 0, 0, 0), "l12e": (12, 29, 1, 2, 5, 2, 1, 2)}
+
+
+@pytest.mark.parametrize("key", list(_LANE_SUBSET_CONTENTS))
+@pytest.mark.parametrize("troe3", [False, True], ids=["troe4", "troe3"])
+def test_generated_lane_mechanisms(pkg, tmp_path, key, troe3):
+    """The GRI-Mech subsets of tests/test_lane_kernels.py are what the lane-engine tests need: gas only,
+    n = 9 (k_lane<9>) and n = 12 (k_lane<12>), a Troe reaction in both (4 parameters; 3 for the first one
+    with troe3), in l12e also a Lindemann, two irreversible and one three-product reaction, third-body
+    efficiencies other than 1 on the falloff reactions; and br_mech_parse compiles them to the Python
+    compiler's tables bit for bit."""
+    from test_group_kernels import subset_mechanism
+    from test_lane_kernels import LANE_SUBSETS
+    species = LANE_SUBSETS[key]
+    d = subset_mechanism(tmp_path, species, troe3=troe3)
+    m = pkg.Mechanism.from_files(d, gas_mech="mech.dat")
+    t = m.tables
+    n, nrg, n_lind, n_troe, n_tb, n_irr, n_p3, n_slots3 = _LANE_SUBSET_CONTENTS[key]
+    assert m.ns == 0 and m.n == n and m.gas_species == species and m.nrg == nrg
+    fo = t["g_tb"] == 2
+    assert int(np.sum(fo & (t["g_troe_n"] == 0))) == n_lind
+    assert int(np.sum(fo & (t["g_troe_n"] > 0))) == n_troe
+    assert int(np.sum(fo & (t["g_troe_n"] == 3))) == int(troe3)
+    assert int(np.sum(fo & (t["g_troe_n"] == 4))) == n_troe - int(troe3)
+    assert int(np.sum(t["g_tb"] == 1)) == n_tb
+    assert int(np.sum(t["g_rev"] == 0)) == n_irr
+    slots3 = [r for r in range(m.nrg) if t["g_nr"][r] == 3]
+    p3 = [r for r in slots3 if not set(t["g_f"][r, :t["g_nf"][r]]) & set(t["g_r"][r, :3])]
+    assert (len(p3), len(slots3)) == (n_p3, n_slots3) and t["g_nf"].max() <= 3 and t["g_nr"].max() <= 3
+    for r in np.flatnonzero(fo):   # (the em1 columns of lane_jac run together with the falloff terms)
+        assert np.any(t["g_eff"][r] != 1.0), r
+    rc, nat = _native(pkg, os.path.join(d, "mech.dat"), None)
+    assert rc == 0, nat
+    assert nat["sizes"] == (m.ng, 0, m.nrg, 0) and nat["names"] == m.species
+    py = dict(t, molwt=m.molwt, nasa=m.nasa, sigma=m.sigma)
+    for f in _DESC_SHAPES:
+        a, b = nat[f], np.asarray(py[f])
+        if a is None:
+            assert b.size == 0, f
+        elif a.dtype.kind == "f":
+            assert a.shape == b.shape, f
+            assert np.array_equal(a.view(np.uint64), np.ascontiguousarray(b, np.float64).view(np.uint64)), f
+        else:
+            assert a.shape == b.shape and np.array_equal(a, b), f
+
+
 def test_native_compiler_errors(pkg, tmp_path):
     """Bad inputs come back as BR_ERR_INPUT with a message (no exception crosses the C-ABI)."""
     rc, msg = _native(pkg, "nonexistent.dat")
