@@ -28,13 +28,15 @@ class MechDesc(C.Structure):
 class Opts(C.Structure):
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_steps", C.c_int), ("device", C.c_int),
                 ("hmax", C.c_double), ("trace_cap", C.c_int), ("unstable_factor", C.c_double),
-                ("ignition_species", C.c_int), ("nout", C.c_int), ("tout", dp), ("yout", dp),
+                ("ignition_species", C.c_int), ("energy", C.c_int), ("T_end", dp), ("T_out", dp),
+                ("nout", C.c_int), ("tout", dp), ("yout", dp),
                 ("ntprog", C.c_int), ("tprog_t", dp), ("tprog_T", dp), ("ntprog_rows", C.c_int), ("tprog_row", ip),
                 ("dq_jacobian", C.c_int), ("nmult", C.c_int), ("rate_mult", dp), ("rate_mult_row", ip),
                 ("tout_per_reactor", C.c_int)]
 
 
 NSTAT = 20
+ENERGY_ADIABATIC_V = 1   # br_opts.energy: adiabatic constant-volume reactor
 BATCH_MAXCOMP = 64
 
 
@@ -53,7 +55,7 @@ EXPORTS = ["br_version", "br_last_error", "br_device_count", "br_mech_create", "
            "br_host_mech_species", "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml",
            "br_integrate_host", "br_phase_tout_dev", "br_integrate_phase", "br_debug_group_eval",
            "br_debug_group_lu_solve", "br_sensitivity", "br_debug_tprog_eval", "br_debug_lane_eval",
-           "br_debug_lane_lu_solve", "br_debug_wave_eval"]
+           "br_debug_lane_lu_solve", "br_debug_wave_eval", "br_debug_energy_eval"]
 
 # br_integrate_host callbacks: int f(void* user, double t, const double* u, double* du);
 # void cb(void* user, double t, const double* u)
@@ -106,6 +108,8 @@ def lib():
     L.br_debug_lane_lu_solve.restype = C.c_int
     L.br_debug_wave_eval.argtypes = [vp, C.c_int, dp, dp, dp, dp, C.c_int, dp, ip, dp, dp]
     L.br_debug_wave_eval.restype = C.c_int
+    L.br_debug_energy_eval.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, ip, dp]
+    L.br_debug_energy_eval.restype = C.c_int
     cs = C.c_char_p
     L.br_mech_parse.argtypes = [cs, cs, cs, cs, C.c_int, C.POINTER(vp)]
     L.br_host_mech_desc.argtypes = [vp, C.POINTER(MechDesc)]

@@ -28,6 +28,7 @@ namespace {
 #include "brhip_group.hpp"   // group engines: 4 / 2 reactors per wave (16- / 32-lane groups, n <= 32)
 #include "brhip_sens.hpp"    // rate-multiplier block, br_sensitivity's expansion and reduction kernels
 #include "brhip_tprog.hpp"   // temperature programmes T(t): the launch's block and the evaluator
+#include "brhip_energy.hpp"  // adiabatic constant-volume reactors: T as component ng of the energy instances
 
 // ------------------------------------------------------------------------------------
 // the integrator kernel: one reactor per 64-lane wavefront, `rpb` reactors per workgroup
@@ -71,14 +72,22 @@ __host__ __device__ constexpr int br_wpe(int nmax) {
 // TPROG: the instances of a temperature-programme run (br_opts.ntprog; brhip_tprog.hpp). They take KOptsProg,
 // do not read Tv, and refresh the T-only constants inside the step loop; everything under
 // `if constexpr (TPROG)` is theirs alone, the isothermal instances compile the source they always had.
-template <int NMAX, bool TPROG = false>
+// ENERGY: the instances of an adiabatic run (br_opts.energy; brhip_energy.hpp), NMAX from ng + 1. They take
+// KOptsEnergy, carry T as component ng (lane ng) of a system of nsys = ng + 1 equations, refresh the constants
+// before any RHS whose T differs from the cached one, and always build CVODE's DQ Jacobian; everything under
+// `if constexpr (ENERGY)` is theirs alone.
+template <int NMAX, bool TPROG = false, bool ENERGY = false>
 __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_per_eu(br_wpe(NMAX), 8))) void k_integrate(
     DevMech M, int N, int rpb, const double* __restrict__ Tv, const double* __restrict__ Asvv, double* __restrict__ U,
-    const double* __restrict__ tfv, std::conditional_t<TPROG, KOptsProg, KOpts> o, br_stats* __restrict__ stats,
-    double* __restrict__ Jws, double* __restrict__ trace) {
+    const double* __restrict__ tfv, std::conditional_t<TPROG, KOptsProg, std::conditional_t<ENERGY, KOptsEnergy, KOpts>> o,
+    br_stats* __restrict__ stats, double* __restrict__ Jws, double* __restrict__ trace) {
+    static_assert(!(TPROG && ENERGY) && (!ENERGY || NMAX <= 56), "energy instances: no programme, one component per lane");
     constexpr int CPL = NMAX > 64 ? 2 : 1;   // components per lane
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const WaveCtx W = wave_ctx<CPL, NMAX>(M, smem_raw, rpb, Jws);
+    const WaveCtx W = [&] {
+        if constexpr (ENERGY) return energy_wave_ctx<NMAX>(M, smem_raw, rpb, Jws);
+        else return wave_ctx<CPL, NMAX>(M, smem_raw, rpb, Jws);
+    }();
     // Reactor indices: with o.work every wave of the (resident-sized) grid keeps taking the next
     // index from the counter until the list is drained, so a wave whose reactor finishes early
     // starts another instead of idling until the slowest reactor of its workgroup is done; the
@@ -102,14 +111,19 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     VA<CPL, 64, vec_stride(NMAX)> V = Vm;
     const RView& S = W.R;
     const int n = M.n;
+    const int nsys = ENERGY ? n + 1 : n;   // equations of the controller, the DQ Jacobian, the LU and the solve
     // T: the temperature the T-only constants in the reactor's slots were built for. Isothermal: the
     // reactor's constant. Programme run: T(t) of the last refresh, wave-uniform, with the reactor's row
-    // and cached segment in tp
+    // and cached segment in tp. Energy run: the clamped T of the last refresh, wave-uniform, with the
+    // lane's e_k and cv_k at it in ek, cvk
     double T;
     [[maybe_unused]] std::conditional_t<TPROG, TProgRow, NoTProgRow> tp;
+    [[maybe_unused]] double ek = 0.0, cvk = 0.0;
     if constexpr (TPROG) {
         tp = tprog_row(o.prog, rid);
         T = uni(tp.eval(o.rid_t0 ? uni(o.rid_t0[idx]) : 0.0));
+    } else if constexpr (ENERGY) {
+        T = energy_tclamp(uni(Tv[rid]));
     } else {
         T = Tv[rid];
     }
@@ -119,23 +133,27 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     double* LUsave = Jsave + NMAX * col_rows(NMAX);
     double* jscr = LUsave;   // (aliases the factors: see rxd_ws_off)
     C->a_rtol = o.rtol; C->a_atol = o.atol; C->a_hmax_inv = o.hmax_inv; C->a_ufac = o.ufac;
-    C->a_max_steps = o.max_steps; C->a_trace_cap = o.trace_cap; C->a_trace = trace; C->a_rid = rid; C->a_n = n;
+    C->a_max_steps = o.max_steps; C->a_trace_cap = o.trace_cap; C->a_rid = rid; C->a_n = nsys;
+    if constexpr (ENERGY) C->a_trace = o.T_out;   // (no trace in an energy run: the slot carries T_out)
+    else C->a_trace = trace;
     C->a_ign = o.ign; C->a_nout = o.nout; C->a_tout = o.tout; C->a_yout = o.yout;
 
     init_tconst<CPL, true>(M, tb, S, T, lane, rid);
+    if constexpr (ENERGY) energy_thermo(lane, n, T, ek, cvk);
 
     // ---- CVodeInit
     double u0[CPL], su = 0.0;
 #pragma unroll
     FOR_S {
-        const bool act = CS < n;
-        u0[s] = act ? U[(size_t)rid * n + CS] : 0.0;
+        const bool act = CS < nsys;
+        if constexpr (ENERGY) u0[s] = CS < n ? U[(size_t)rid * n + CS] : (CS == n ? uni(Tv[rid]) : 0.0);   // lane ng: T(0)
+        else u0[s] = act ? U[(size_t)rid * n + CS] : 0.0;
 #pragma unroll
         for (int j = 0; j < NVEC; ++j) V.at(j, s) = 0.0;
         V.at(0, s) = u0[s];
         V.at(V_Y, s) = u0[s];
         V.at(V_EWT, s) = act ? 1.0 / (o.rtol * fabs(u0[s]) + o.atol) : 1.0;
-        su += act ? fabs(u0[s]) : 0.0;
+        su += (ENERGY ? CS < n : act) ? fabs(u0[s]) : 0.0;   // (the runaway limit is on the species)
     }
 #pragma unroll
     for (int i = 0; i < QMAX + 2; ++i) C->tau[i] = 0.0;
@@ -184,6 +202,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
             if (!o.rid_t0)                                  // (a continued reactor wrote them already)
 #pragma unroll
                 FOR_S if (CS < n) o.yout[((size_t)rid * o.nout + io) * n + CS] = u0[s];
+            if constexpr (ENERGY) { if (o.T_out && lane == n) o.T_out[(size_t)rid * o.nout + io] = u0[0]; }
             ++io;
         }
         C->iout = io;
@@ -212,6 +231,21 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
             }
         }
     };
+    // Energy run, before an RHS: T is component ng of the y it is evaluated at, clamped. Bitwise the cached T
+    // (the species columns of a DQ Jacobian, a Newton iterate that left T alone): the constants stand. Else
+    // tprog_refresh's sequence, and lane k recomputes its e_k and cv_k. The T column of a DQ Jacobian
+    // refreshes once, the RHS after it refreshes back.
+    auto energy_refresh = [&](double yl) {
+        if constexpr (ENERGY) {
+            const double Tc = energy_tclamp(uni(bcast(yl, n)));
+            if (__double_as_longlong(Tc) != __double_as_longlong(T)) {
+                T = Tc;
+                wave_sync();
+                init_tconst<CPL, true>(M, tb, S, T, lane, rid);
+                energy_thermo(lane, n, T, ek, cvk);
+            }
+        }
+    };
     for (;;) {
         double y[CPL], f[CPL];
 #pragma unroll
@@ -225,7 +259,12 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         {
             BR_CLK(c0);
             tprog_refresh();
+            energy_refresh(y[0]);
             rhs<CPL>(M, tb, S, T, Asv, Asv_th, y, lane, p_last, f);
+            if constexpr (ENERGY) {   // f[ng] = dT/dt from the du just computed (lane ng's f was 0)
+                const double Td = energy_tdot(tb, lane, n, y[0], f[0], ek, cvk);
+                if (lane == n) f[0] = Td;
+            }
             BR_X_AFTER_RHS();
             BR_ACC(cyc_rhs, c0);
         }
@@ -236,7 +275,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
             BR_CLK(c0);
             dq_column<CPL>(C, V, lane, dqj, f, Jsave);
             BR_ACC(cyc_jac, c0);
-            if (++dqj < n) continue;
+            if (++dqj < nsys) continue;
             dqj = -1;
             dq_newton_rhs<CPL>(C, V, lane, b);
             act_code = A_SETUP;
@@ -244,7 +283,8 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         } else {
             BR_CLK(c2);
             BR_SUB_T(pr0);
-            act_code = ctl_post_rhs<CPL>(C, V, lane, f, b);
+            if constexpr (ENERGY) act_code = ctl_post_rhs<CPL, 64, vec_stride(NMAX), true>(C, V, lane, f, b);
+            else act_code = ctl_post_rhs<CPL>(C, V, lane, f, b);
             BR_SUB_ADD(3, pr0);
             BR_ACC(cyc_ctl, c2);
             if (act_code == A_RHS) continue;
@@ -257,6 +297,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         }
         int lu_fail = 0;
         if (act_code == A_SETUP) {
+            if constexpr (!ENERGY) {   // (an energy run's o.dq_jac is always set: every new J came from the DQ columns)
             if (!jac_ready && ui(C->newj)) {
                 BR_CLK(c0);
                 tprog_refresh();   // (the tn of the RHS just before: no refresh in practice)
@@ -264,9 +305,10 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
                 BR_X_AFTER_JAC();
                 BR_ACC(cyc_jac, c0);
             }
+            }
             BR_CLK(c1);
-            if constexpr (CPL == 1) lu_fail = lu_factor<NMAX>(Jsave, LUsave, ud(C->gamma), n, lane, perm[0]);
-            else lu_fail = lu_factor2<NMAX>(Jsave, LUsave, scr, ud(C->gamma), n, lane, perm);
+            if constexpr (CPL == 1) lu_fail = lu_factor<NMAX>(Jsave, LUsave, ud(C->gamma), nsys, lane, perm[0]);
+            else lu_fail = lu_factor2<NMAX>(Jsave, LUsave, scr, ud(C->gamma), nsys, lane, perm);
             BR_ACC(cyc_lu, c1);
         }
         double delta[CPL];
@@ -275,10 +317,10 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         if (!lu_fail) {
             BR_CLK(c0);
             if constexpr (CPL == 1) {
-                delta[0] = lu_solve<NMAX>(LUsave, n, lane, perm[0], b[0], scr);
+                delta[0] = lu_solve<NMAX>(LUsave, nsys, lane, perm[0], b[0], scr);
                 BR_X_AFTER_SOLVE();
             } else {
-                lu_solve2<NMAX>(LUsave, scr, n, lane, perm, b);
+                lu_solve2<NMAX>(LUsave, scr, nsys, lane, perm, b);
                 delta[0] = b[0];
                 delta[1] = b[1];
             }
@@ -286,7 +328,8 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
         }
         BR_X_AFTER_ITER();
         BR_CLK(c3);
-        act_code = ctl_post_solve<CPL>(C, V, lane, delta, lu_fail);
+        if constexpr (ENERGY) act_code = ctl_post_solve<CPL, 64, vec_stride(NMAX), true>(C, V, lane, delta, lu_fail);
+        else act_code = ctl_post_solve<CPL>(C, V, lane, delta, lu_fail);
         BR_ACC(cyc_ctl, c3);
         if (act_code == A_DONE) break;
     }
@@ -295,6 +338,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     FOR_S {
         const double u_out = status ? V.at(0, s) : V.at(V_Y, s);
         if (CS < n) U[(size_t)rid * n + CS] = u_out;
+        if constexpr (ENERGY) { if (o.T_end && CS == n) o.T_end[rid] = u_out; }
     }
     if (stats && lane == 0) {
         br_stats& s = stats[rid];
@@ -444,6 +488,10 @@ static const void* wave_tprog_kernel(int nmax) {   // ... of a temperature-progr
          : nmax == 56 ? (const void*)k_integrate<56, true> : nmax == 64 ? (const void*)k_integrate<64, true>
                                                                         : (const void*)k_integrate<72, true>;
 }
+static const void* wave_energy_kernel(int nmax) {   // ... of an adiabatic run, nmax from ng + 1 <= 56
+    return nmax == 16 ? (const void*)k_integrate<16, false, true> : nmax == 32 ? (const void*)k_integrate<32, false, true>
+         : nmax == 56 ? (const void*)k_integrate<56, false, true> : nullptr;
+}
 static const void* lane_kernel(int nm) { return nm == 9 ? (const void*)k_lane<9> : (const void*)k_lane<12>; }
 // the parity kernels, by components per lane
 static const void* rates_kernel(int cpl) { return cpl == 2 ? (const void*)k_rates<2> : (const void*)k_rates<1>; }
@@ -494,6 +542,10 @@ struct br_mech {
     DevBuf wq;                   // int: k_integrate work counter
     DevBuf defer_t0;             // double[DEFER_CAP]: start time of each deferred lane reactor
     int ncu = 0;
+    // energy runs (brhip_energy.hpp): the instance width from ng + 1 and its own launch shape, found at the
+    // first such run (energy_shape); e_nmax = 0: not looked for yet
+    int e_nmax = 0, e_rpb = 0, e_waves_per_cu = 0;
+    size_t e_shmem = 0;
     MultBlock* mult_hdr = nullptr;   // the 32 bytes in front of the g_par table (br_opts.rate_mult; brhip_device.hpp)
 };
 
@@ -541,7 +593,7 @@ struct Stage {
 
 extern "C" {
 
-int br_version(void) { return 220; }   // 220: br_opts grew (temperature programmes between yout and dq_jacobian)
+int br_version(void) { return 230; }   // 230: br_opts grew (energy, T_end, T_out between tprog_row and dq_jacobian)
 const char* br_last_error(void) { return g_err.c_str(); }
 int br_device_count(void) {
     int c = 0;
@@ -907,6 +959,45 @@ static void stage_tprog(Stage& st, int N, const br_opts* opts, br_opts* od) {
     }
 }
 
+// an energy run of a br_opts: the checks that need no handle (a bad value, together with a programme) ...
+static int energy_request(const br_opts* opts) {
+    if (!opts || opts->energy == 0) return 0;
+    if (opts->energy != BR_ENERGY_ADIABATIC_V)
+        return fail(BR_ERR_INPUT, "br_opts.energy = " + std::to_string(opts->energy) + ": 0 or BR_ENERGY_ADIABATIC_V (1)");
+    if (opts->ntprog != 0)
+        return fail(BR_ERR_INPUT, "br_opts.energy together with a temperature programme (br_opts.ntprog): T is either "
+                                  "integrated or prescribed");
+    return 0;
+}
+// ... and those on the mechanism, with the launch shape of its energy instance (the occupancy search of
+// br_mech_create on that kernel and its LDS block), kept in the handle
+static int energy_shape(br_mech* m) {
+    if (m->ns > 0)
+        return fail(BR_ERR_UNSUPPORTED, "br_opts.energy: mechanisms with surface species are not supported (gas-only)");
+    if (m->ng + 1 > 56)
+        return fail(BR_ERR_UNSUPPORTED, "br_opts.energy: ng + 1 = " + std::to_string(m->ng + 1) +
+                                            " components exceed the 56 of the widest energy instance");
+    if (m->e_nmax) return 0;
+    const int nmax = nmax_of(m->ng + 1);
+    const void* kfn = wave_energy_kernel(nmax);
+    int best = 0, best_w = 0;
+    for (int rpb = 1; rpb <= br_maxrpb(nmax); ++rpb) {
+        const size_t b = energy_wg_lds_bytes(m->dm, nmax, rpb);
+        if (b > LDS_PER_CU) break;
+        if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b) != hipSuccess) break;
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 64 * rpb, b) != hipSuccess) break;
+        nb = std::min(nb, (int)(LDS_PER_CU / ((b + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
+        if (nb * rpb > best_w) { best_w = nb * rpb; best = rpb; }
+    }
+    if (best_w == 0) return fail(BR_ERR_UNSUPPORTED, "br_opts.energy: mechanism too large for LDS");
+    m->e_rpb = best;
+    m->e_waves_per_cu = best_w;
+    m->e_shmem = energy_wg_lds_bytes(m->dm, nmax, best);
+    m->e_nmax = nmax;
+    return 0;
+}
+
 // the kernel options of a run: br_opts with its defaults filled in (no work list, no deferral)
 static KOpts make_kopts(const br_mech* m, const br_opts* opts, bool traced) {
     KOpts o;
@@ -948,13 +1039,36 @@ static int launch_wave(br_mech* m, const DevMech& dm, int N, int nwg, const doub
     return 0;
 }
 
+// k_integrate<NMAX, false, true> of an energy run on `nwg` workgroups of m->e_rpb reactors each
+static int launch_wave_energy(br_mech* m, const DevMech& dm, int N, int nwg, const double* dT, const double* dAsv, double* du,
+                              const double* dtf, const KOpts& o, double* T_end, double* T_out, br_stats* dstats, hipStream_t s) {
+    const void* fn = wave_energy_kernel(m->e_nmax);
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->e_shmem));
+    const int rpb = m->e_rpb;
+    double* jws = m->jws.as<double>();
+    double* trace = nullptr;
+    KOptsEnergy oe;
+    static_cast<KOpts&>(oe) = o;
+    oe.T_end = T_end;
+    oe.T_out = o.nout ? T_out : nullptr;
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf,
+                    (void*)&oe, (void*)&dstats, (void*)&jws, (void*)&trace};
+    HIPCHK(hipLaunchKernel(fn, dim3(nwg), dim3(64 * rpb), args, m->e_shmem, s));
+    return 0;
+}
+
 static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv, double* du, const double* dtf,
                          const br_opts* opts, br_stats* dstats, void* stream, double* trace) {
+    if (const int rc = energy_request(opts)) return rc;   // (before the handle is looked at, as the programme checks)
     const bool prog = opts && opts->ntprog != 0;   // a temperature programme: dT is not read
+    const bool energy = opts && opts->energy != 0;
     if (!m || N < 0 || (!dT && !prog) || !du || !dtf) return fail(BR_ERR_INPUT, "bad argument");
     if (const int rc = tprog_request(N, opts)) return rc;
+    if (energy && trace)
+        return fail(BR_ERR_UNSUPPORTED, "br_integrate_traced does not take br_opts.energy: the trace row has no T column");
     if (N == 0) return 0;
     HIPCHK(hipSetDevice(m->device));
+    if (energy) { if (const int rc = energy_shape(m)) return rc; }
     KOpts o = make_kopts(m, opts, trace != nullptr);
     hipStream_t s = (hipStream_t)stream;
     DevMech dm = m->dm;
@@ -965,6 +1079,26 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
         hipLaunchKernelGGL(k_mult_block, dim3(1), dim3(64), 0, s, m->mult_hdr, opts->rate_mult, opts->rate_mult_row);
         HIPCHK(hipGetLastError());
         dm.g_par = reinterpret_cast<const double*>(reinterpret_cast<size_t>(dm.g_par) | 1u);
+    }
+    if (energy) {
+        // the wavefront engine's persistent grid (below) on the energy instance and its shape, CVODE's DQ Jacobian
+        o.dq_jac = 1;
+        const int rpb = m->e_rpb;
+        const char* st_env = getenv("BRHIP_STATIC");
+        const bool dyn = !(st_env && atoi(st_env) == 1) && m->ncu > 0 && m->e_waves_per_cu >= rpb;
+        const int nwg_all = (N + rpb - 1) / rpb;
+        const int nwg = dyn ? std::min(nwg_all, m->ncu * (m->e_waves_per_cu / rpb)) : nwg_all;
+        HIPCHK(m->jws.ensure(jws_bytes(m, nwg * rpb)));   // (slots of the 64-wide layout: no narrower than e_nmax's)
+        if (dyn) {
+            HIPCHK(m->wq.ensure(sizeof(int)));
+            HIPCHK(hipMemsetAsync(m->wq.p, 0, sizeof(int), s));
+            o.work = m->wq.as<int>();
+        }
+        HIPCHK(hipEventRecord(m->ev0, s));
+        if (const int rc = launch_wave_energy(m, dm, N, nwg, dT, dAsv, du, dtf, o, opts->T_end, opts->T_out, dstats, s)) return rc;
+        HIPCHK(hipEventRecord(m->ev1, s));
+        m->ev_recorded = true;
+        return 0;
     }
     const int engine = (trace || prog) ? 0 : pick_engine(m);   // traced and programme runs: the wavefront engine
     const TProg tp = prog ? TProg{opts->tprog_t, opts->tprog_T, opts->tprog_row, opts->ntprog, 0} : TProg{};
@@ -1083,9 +1217,13 @@ static int check_tout_rows(int N, int nout, const double* tout) {
 static int integrate_host(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                           const br_opts* opts, br_stats* stats, double* trace) {
     // (the programme first: its checks need no handle, and with one the T argument may be NULL)
+    if (const int rc = energy_request(opts)) return rc;
     if (N >= 0) { if (const int rc = check_tprog_host(N, opts)) return rc; }
     const bool prog = opts && opts->ntprog != 0;
+    const bool energy = opts && opts->energy != 0;
     if (!m || N < 0 || (!T && !prog) || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
+    if (energy && trace)
+        return fail(BR_ERR_UNSUPPORTED, "br_integrate_traced does not take br_opts.energy: the trace row has no T column");
     if (N == 0) return 0;
     HIPCHK(hipSetDevice(m->device));
     const int n = m->n;
@@ -1105,8 +1243,11 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
         if (!(opts->tout[i] >= opts->tout[i - 1])) return fail(BR_ERR_INPUT, "tout must be ascending");
     if (const int rc = check_mult_host(m, N, opts)) return rc;
     Stage st;
+    // an energy run's T outputs: T_end[N], T_out[N][nout] (staged with the caller's values: entries without an
+    // output keep them, as the rows of yout)
+    const size_t nTe = (energy && opts->T_end) ? (size_t)N : 0, nTo = (energy && opts->T_out) ? (size_t)N * nout : 0;
     HIPCHK(st.reserve(m, (size_t)N * (3 + n + BR_NSTAT) + ntr + nto + nyo + mult_stage_doubles(m, N, opts) +
-                             tprog_stage_doubles(N, opts)));
+                             tprog_stage_doubles(N, opts) + nTe + nTo));
     double* dT = st.take(N);
     double* dA = st.take(N);
     double* dtf = st.take(N);
@@ -1122,6 +1263,10 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
     }
     stage_mult(st, m, N, opts, &od);
     stage_tprog(st, N, opts, &od);
+    if (energy) {
+        od.T_end = nTe ? st.take(nTe) : nullptr;
+        od.T_out = nTo ? st.push(opts->T_out, nTo) : nullptr;
+    }
     st.put(dT, T, N);
     st.put(dA, Asv, N);
     st.put(dtf, tf, N);
@@ -1136,6 +1281,8 @@ static int integrate_host(br_mech* m, int N, const double* T, const double* Asv,
     if (stats) HIPCHK(hipMemcpy(stats, dst, (size_t)N * BR_NSTAT * sizeof(double), hipMemcpyDeviceToHost));
     if (trace) HIPCHK(hipMemcpy(trace, dtr, ntr * sizeof(double), hipMemcpyDeviceToHost));
     if (nout) HIPCHK(hipMemcpy(opts->yout, dyo, nyo * sizeof(double), hipMemcpyDeviceToHost));
+    if (nTe) HIPCHK(hipMemcpy(opts->T_end, od.T_end, nTe * sizeof(double), hipMemcpyDeviceToHost));
+    if (nTo) HIPCHK(hipMemcpy(opts->T_out, od.T_out, nTo * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1151,6 +1298,7 @@ int br_integrate_traced(br_mech* m, int N, const double* T, const double* Asv, d
 
 int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, const double* Asv, double* u,
                        const double* tf, const br_opts* opts, br_stats* stats) {
+    if (const int rc0 = energy_request(opts)) return rc0;
     if (N >= 0) { if (const int rc0 = check_tprog_host(N, opts)) return rc0; }   // (indices of the ensemble in the message)
     const bool prog = opts && opts->ntprog != 0;
     if (!mechs || ndev < 1 || N < 0 || (!T && !prog) || !u || !tf) return fail(BR_ERR_INPUT, "bad argument");
@@ -1180,6 +1328,10 @@ int br_integrate_multi(br_mech* const* mechs, int ndev, int N, const double* T, 
             if (opts) od = *opts;
             if (nout) od.yout = opts->yout + (size_t)start * nout * n;
             if (per) od.tout = opts->tout + (size_t)start * nout;
+            if (opts && opts->energy) {   // the slice's T outputs
+                if (opts->T_end) od.T_end = opts->T_end + start;
+                if (opts->T_out) od.T_out = opts->T_out + (size_t)start * nout;
+            }
             if (opts && opts->nmult > 0) {   // the slice's row indices, or its rows of the dense table
                 if (opts->rate_mult_row) od.rate_mult_row = opts->rate_mult_row + start;
                 else { od.rate_mult = opts->rate_mult + (size_t)start * nr; od.nmult = cnt; }
@@ -1216,6 +1368,7 @@ int br_phase_tout_dev(int N, br_stats* dstats, int ntau, const double* dtau, con
 
 int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                        const br_opts* opts, br_stats* stats, int ntau, const double* tau, double* tout, double* yout) {
+    if (const int rce = energy_request(opts)) return rce;
     if (N >= 0) { if (const int rcp = check_tprog_host(N, opts)) return rcp; }
     const bool prog = opts && opts->ntprog != 0;
     if (!m || N < 0 || (!T && !prog) || !u || !tf || !tau || !tout || !yout || ntau < 1) return fail(BR_ERR_INPUT, "bad argument");
@@ -1230,8 +1383,11 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
     const size_t nu = (size_t)N * n, nto = (size_t)N * ntau, nyo = nto * n;
     if (const int rcm = check_mult_host(m, N, opts)) return rcm;
     Stage st;
+    // an energy run: both passes run with it; opts->T_end [N] and opts->T_out [N][ntau] (T at the phases; entries
+    // of NaN times are left untouched) are pass 2's
+    const size_t nTe = (opts->energy && opts->T_end) ? (size_t)N : 0, nTo = (opts->energy && opts->T_out) ? nto : 0;
     HIPCHK(st.reserve(m, (size_t)N * (3 + BR_NSTAT) + 2 * nu + ntau + nto + nyo + mult_stage_doubles(m, N, opts) +
-                             tprog_stage_doubles(N, opts)));
+                             tprog_stage_doubles(N, opts) + nTe + nTo));
     double* dT = st.push(T, N);
     double* dA = st.push(Asv, N);
     double* dtf = st.push(tf, N);
@@ -1244,10 +1400,13 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
     br_opts od = *opts;
     stage_mult(st, m, N, opts, &od);   // (both passes run with the same multipliers)
     stage_tprog(st, N, opts, &od);     // (... and the same programmes)
+    double* dTe = nTe ? st.take(nTe) : nullptr;
+    double* dTo = nTo ? st.push(opts->T_out, nTo) : nullptr;
     HIPCHK(st.err);
     od.trace_cap = 0;
     // pass 1: no outputs, for t_ign
     od.nout = 0; od.tout = nullptr; od.yout = nullptr; od.tout_per_reactor = 0;
+    od.T_end = nullptr; od.T_out = nullptr;
     HIPCHK(hipMemcpyAsync(du_, du0, nu * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
     int rc = integrate_dev(m, N, dT, Asv ? dA : nullptr, du_, dtf, &od, (br_stats*)dst, nullptr, nullptr);
     if (rc) return rc;
@@ -1255,6 +1414,7 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
     if (rc) return rc;
     // pass 2: the same u0 and options (the same steps) with the per-reactor grid
     od.nout = ntau; od.tout = dto; od.yout = dyo; od.tout_per_reactor = 1;
+    od.T_end = dTe; od.T_out = dTo;
     HIPCHK(hipMemcpyAsync(du_, du0, nu * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
     rc = integrate_dev(m, N, dT, Asv ? dA : nullptr, du_, dtf, &od, (br_stats*)dst, nullptr, nullptr);
     if (rc) return rc;
@@ -1263,6 +1423,8 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
     if (stats) HIPCHK(hipMemcpy(stats, dst, (size_t)N * BR_NSTAT * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(tout, dto, nto * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(yout, dyo, nyo * sizeof(double), hipMemcpyDeviceToHost));
+    if (nTe) HIPCHK(hipMemcpy(opts->T_end, dTe, nTe * sizeof(double), hipMemcpyDeviceToHost));
+    if (nTo) HIPCHK(hipMemcpy(opts->T_out, dTo, nTo * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1275,6 +1437,7 @@ int br_sensitivity(br_mech* m, int N, const double* T, const double* Asv, const 
                    br_stats* stats, long long* nbad) {
     if (opts && opts->ntprog != 0)   // (before anything else: no handle, no device needed to learn it)
         return fail(BR_ERR_UNSUPPORTED, "br_sensitivity does not take a temperature programme (br_opts.ntprog)");
+    if (const int rce = energy_request(opts)) return rce;
     if (!m || N < 0 || !T || !u0 || !tf) return fail(BR_ERR_INPUT, "bad argument");
     if (!(factor > 1.0) || !(factor < INFINITY)) return fail(BR_ERR_INPUT, "factor must be finite and > 1");
     if (opts && (opts->nmult != 0 || opts->rate_mult))
@@ -1324,6 +1487,7 @@ int br_sensitivity(br_mech* m, int N, const double* T, const double* Asv, const 
     if (opts) od = *opts;
     od.trace_cap = 0; od.nout = 0; od.tout = nullptr; od.yout = nullptr; od.tout_per_reactor = 0;
     od.nmult = rows; od.rate_mult = dtab; od.rate_mult_row = erow;
+    od.T_end = nullptr; od.T_out = nullptr;   // (an energy run's expanded reactors: no T outputs)
     const double den = 2.0 * std::log(factor);
     auto blocks = [](size_t ne) { return dim3((unsigned)((ne + 255) / 256)); };
     for (int i0 = 0; i0 < N; i0 += B0) {

@@ -16,6 +16,19 @@ __device__ __forceinline__ double nasa_grt(int k, double T, double lT) {
     return h - s;
 }
 
+// h/RT and cp/R of species k (NASA-7, the branch rule of nasa_grt); the energy instances of k_integrate
+// (brhip_energy.hpp) are their only callers
+__device__ __forceinline__ double nasa_hrt(int k, double T) {
+    const double* c = MF(nasa) + 15 * k;
+    const double* a = (T < c[0]) ? c + 8 : c + 1;
+    return a[0] + a[1] * T / 2 + a[2] * T * T / 3 + a[3] * T * T * T / 4 + a[4] * T * T * T * T / 5 + a[5] / T;
+}
+__device__ __forceinline__ double nasa_cpr(int k, double T) {
+    const double* c = MF(nasa) + 15 * k;
+    const double* a = (T < c[0]) ? c + 8 : c + 1;
+    return a[0] + a[1] * T + a[2] * T * T + a[3] * T * T * T + a[4] * T * T * T * T;
+}
+
 // T-only constants of gas reaction r: kd[2r] = kf, kd[2r+1] = kr = kf / Kc (grt: g/RT per species), and
 // for a falloff reaction its {k0/k_inf, log10 Fcent, c, n} in fod. mr: the reactor's rate multipliers
 // (MULT = false: a kernel that never sees a tagged g_par, see MultBlock)

@@ -426,7 +426,9 @@ __device__ __forceinline__ void track_ignition(LCtl* C, const CtlArgs& a, int la
 }
 // dense output (CVode CV_NORMAL): every tout in (t_{n-1}, t_n] from the Nordsieck array of the step
 // just completed, y(t) = sum_j z_j ((t - tn)/h)^j (CVodeGetDky, k = 0)
-template <int CPL, int GW = 64, int VS = GW>
+// (EN, the energy instances: a.n = ng + 1, the yout rows keep ng entries, lane ng's value -- T -- goes to
+// T_out[orow], which rides in a.trace: an energy run takes no trace)
+template <int CPL, int GW = 64, int VS = GW, bool EN = false>
 __device__ __forceinline__ void dense_output(LCtl* C, VA<CPL, GW, VS>& V, const CtlArgs& a, int lane, double tn, double h, int q,
                                              double tlim) {
     int io = gui<GW>(C->iout);
@@ -437,13 +439,18 @@ __device__ __forceinline__ void dense_output(LCtl* C, VA<CPL, GW, VS>& V, const 
         const double t = guni<GW>(tout_at<(GW < 64)>(a.tout, orow, io));
         if (!(t <= tlim)) break;
         const double sk = (t - tn) / h;
-        auto row = a.yout + orow * a.n;
+        auto row = a.yout + orow * (EN ? a.n - 1 : a.n);
 #pragma unroll
         FOR_S {
             double yv = vget<CPL>(V, q, s);
 #pragma unroll
             for (int j = QMAX - 1; j >= 0; --j) if (j < q) yv = V.at(j, s) + sk * yv;
-            if (CS < a.n) row[CS] = yv;
+            if constexpr (EN) {
+                if (CS < a.n - 1) row[CS] = yv;
+                else if (CS == a.n - 1 && a.trace) a.trace[orow] = yv;
+            } else {
+                if (CS < a.n) row[CS] = yv;
+            }
         }
         ++io;
     }
@@ -850,7 +857,7 @@ __device__ __forceinline__ double ctl_rhs_time(LCtl* C) {
 // Controller, part 1: after the RHS value f = F(y) of this lane is known.
 // Returns A_RHS (next y in V[V_Y]), A_SOLVE (delta for the solve returned in *rhs_out),
 // A_SETUP (Jacobian decision in C->newj, then LU and solve), A_DONE.
-template <int CPL, int GW = 64, int VS = GW>
+template <int CPL, int GW = 64, int VS = GW, bool EN = false>
 __device__ BR_CTL_INLINE int ctl_post_rhs(LCtl* C, VA<CPL, GW, VS>& V, int lane, const double (&f)[CPL], double (&rhs_out)[CPL]) {
     const CtlArgs a = load_args<GW>(C);
     const int n = a.n;
@@ -957,7 +964,7 @@ __device__ BR_CTL_INLINE int ctl_post_rhs(LCtl* C, VA<CPL, GW, VS>& V, int lane,
     const double tn = ud(C->tn), tstop = ud(C->tstop);
     if ((tn + h - tstop) * h > 0.0) h = (tstop - tn) * (1.0 - 4.0 * UROUND);
     C->h = h; C->hscale = h; C->hprime = h;
-    trace_row<CPL, GW>(C, a, lane, 0, 0.0, z0, z0);
+    if constexpr (!EN) trace_row<CPL, GW>(C, a, lane, 0, 0.0, z0, z0);   // (EN: a.trace is T_out, dense_output)
 #pragma unroll
     FOR_S V.at(1, s) *= h;
     if (a.max_steps <= 0) { C->status = BR_ERR_MAXSTEPS; return A_DONE; }
@@ -992,7 +999,9 @@ __device__ __forceinline__ double pow_int(double x, int L) {
 // Controller, part 2: after the linear solve (delta = this lane's Newton correction) or after
 // an LU failure (lu_fail != 0). Runs the convergence test, the error test, cvCompleteStep,
 // cvPrepareNextStep and the tstop logic; returns A_RHS (next y in V[V_Y]) or A_DONE.
-template <int CPL, int GW = 64, int VS = GW>
+// (EN, the energy instances: component n - 1 is T. The NaN check covers it, the runaway test against ulimit
+// does not; no trace rows; the dense output writes T_out)
+template <int CPL, int GW = 64, int VS = GW, bool EN = false>
 __device__ BR_CTL_INLINE int ctl_post_solve(LCtl* C, VA<CPL, GW, VS>& V, int lane, double (&delta)[CPL], int lu_fail) {
     BR_SUB_T(ps0);
     BR_QMARK(ps_start);
@@ -1216,11 +1225,15 @@ __device__ BR_CTL_INLINE int ctl_post_solve(LCtl* C, VA<CPL, GW, VS>& V, int lan
         // first, as in the oracle: an unstable step writes no trace row and no dense output
         double zm = 0.0;
 #pragma unroll
-        FOR_S if (CS < n) { const double a = fabs(z0[s]); zm = fmax(zm, a == a ? a : INFINITY); }
+        FOR_S if (CS < n) {
+            const double a = fabs(z0[s]);
+            if constexpr (EN) zm = fmax(zm, a == a ? (CS == n - 1 && a < INFINITY ? 0.0 : a) : INFINITY);
+            else zm = fmax(zm, a == a ? a : INFINITY);
+        }
         const double mx = guni<GW>(gmax<GW>(zm));
         if (!(mx < INFINITY) || mx > ulimit) { C->status = BR_ERR_UNSTABLE; return A_DONE; }
     }
-    if (a.trace) {
+    if (!EN && a.trace) {
         double yl[CPL];
 #pragma unroll
         FOR_S yl[s] = V.at(V_Y, s);                     // the last RHS was evaluated at y
@@ -1229,12 +1242,12 @@ __device__ BR_CTL_INLINE int ctl_post_solve(LCtl* C, VA<CPL, GW, VS>& V, int lan
     BR_QMARK(ps_ignition);
     if (a.ign >= 0) track_ignition<CPL, GW>(C, a, lane, tn, z0);
     BR_QMARK(ps_dense);
-    if (a.nout) dense_output<CPL, GW>(C, V, a, lane, tn, h, q, tn);
+    if (a.nout) dense_output<CPL, GW, VS, EN>(C, V, a, lane, tn, h, q, tn);
     // CVode ONE_STEP + tstop handling
     BR_QMARK(ps_tstop);
     const double troundoff = FUZZ * UROUND * (fabs(tn) + fabs(h));
     if (fabs(tn - tstop) <= troundoff) {                     // CVodeGetDky(tstop, 0)
-        if (a.nout) dense_output<CPL, GW>(C, V, a, lane, tn, h, q, tstop);
+        if (a.nout) dense_output<CPL, GW, VS, EN>(C, V, a, lane, tn, h, q, tstop);
         const double sk = (tstop - tn) / h;
 #pragma unroll
         FOR_S {
@@ -1242,7 +1255,7 @@ __device__ BR_CTL_INLINE int ctl_post_solve(LCtl* C, VA<CPL, GW, VS>& V, int lan
 #pragma unroll
             for (int j = QMAX - 1; j >= 0; --j) if (j < q) yv = V.at(j, s) + sk * yv;
             V.at(V_Y, s) = yv;
-            if (a.trace && nst <= a.trace_cap) {
+            if (!EN && a.trace && nst <= a.trace_cap) {
                 auto row = a.trace + ((size_t)a.rid * (a.trace_cap + 1) + nst) * (2 * n + 4);
                 if (lane == 0 && s == 0) row[0] = tstop;
                 if (CS < n) row[4 + CS] = yv;

@@ -421,8 +421,52 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) void k_wave_eval(DevMech M, i
         }
     }
 }
+
+// ------------------------------------------------------------------------------------
+// energy-run check (tests): the right-hand side of k_integrate<NMAX, false, true> through its own device
+// functions (energy_wave_ctx, energy_tclamp, init_tconst<1, true>, energy_thermo, rhs<1>, energy_tdot), rpb
+// waves per workgroup on one table block, the per-slot workspace of the integrator. Reactors slot, slot + G, ...
+// one after another in the wave's block and slot. Two legs per reactor, as a refresh in a run: the constants
+// and e_k, cv_k are first built at a temperature 150 K above (one discarded evaluation), then rebuilt at T.
+// ------------------------------------------------------------------------------------
+template <int NMAX>
+__global__ __launch_bounds__(64 * br_maxrpb(NMAX)) void k_energy_eval(DevMech M, int N, int rpb, const double* __restrict__ Tv,
+                                                                      const double* __restrict__ U, double* __restrict__ DU,
+                                                                      double* __restrict__ Jws) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const WaveCtx W = energy_wave_ctx<NMAX>(M, smem_raw, rpb, Jws);
+    const int widx = W.rid;
+    const int G = (int)gridDim.x * rpb;
+    const int lane = W.lane;
+    const Tab& tb = W.tb;
+    const RView& S = W.R;
+    const int n = M.n;
+    double* p_last = reinterpret_cast<double*>(W.rbase);
+    for (int rid = widx; rid < N; rid += G) {
+        wave_sync();
+        double y[1], f[1];
+        y[0] = lane < n ? U[(size_t)rid * n + lane] : (lane == n ? uni(Tv[rid]) : 0.0);
+        double T = 0.0, ek = 0.0, cvk = 0.0;
+#pragma unroll 1
+        for (int leg = 0; leg < 2; ++leg) {
+            const double Tl = energy_tclamp(uni(bcast(y[0], n)) + (leg == 0 ? 150.0 : 0.0));
+            T = Tl;
+            if (leg) wave_sync();
+            init_tconst<1, true>(M, tb, S, T, lane, rid);
+            energy_thermo(lane, n, T, ek, cvk);
+            rhs<1>(M, tb, S, T, 1.0, 1.0, y, lane, p_last, f);
+            const double Td = energy_tdot(tb, lane, n, y[0], f[0], ek, cvk);
+            if (lane == n) f[0] = Td;
+        }
+        if (lane <= n) DU[(size_t)rid * (n + 1) + lane] = f[0];
+    }
+}
 }  // namespace
 
+static const void* energy_eval_kernel(int nmax) {
+    return nmax == 16 ? (const void*)k_energy_eval<16> : nmax == 32 ? (const void*)k_energy_eval<32>
+         : nmax == 56 ? (const void*)k_energy_eval<56> : nullptr;
+}
 static const void* lane_eval_kernel(int nm) {
     return nm == 9 ? (const void*)k_lane_eval<9> : nm == 12 ? (const void*)k_lane_eval<12> : nullptr;
 }
@@ -538,6 +582,33 @@ extern "C" int br_debug_wave_eval(br_mech* m, int N, const double* T, const doub
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(J, dJ, (size_t)N * n * n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int br_debug_energy_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
+                                    const int* rate_mult_row, double* du) {
+    if (!m || N <= 0 || !T || !u || !du) return fail(BR_ERR_INPUT, "bad argument");
+    HIPCHK(hipSetDevice(m->device));
+    if (const int rc = energy_shape(m)) return rc;
+    const int n = m->n, rpb = m->e_rpb;
+    const int blocks = std::min(2, (N + 4 * rpb - 1) / (4 * rpb));   // (as br_debug_wave_eval)
+    double *dT, *du_, *ddu, *dws;
+    DevScratch S;
+    DevMech dm = m->dm;
+    if (const int rc = debug_stage_mult(m, N, nmult, rate_mult, rate_mult_row, S, dm)) return rc;
+    HIPCHK(S.alloc(&dT, (size_t)N * 8));
+    HIPCHK(S.alloc(&du_, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&ddu, (size_t)N * (n + 1) * 8));
+    HIPCHK(S.alloc(&dws, (size_t)blocks * rpb * ws_doubles(m->e_nmax, m->nrg) * 8));
+    HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
+    const void* fn = energy_eval_kernel(m->e_nmax);
+    if (!fn) return fail(BR_ERR_UNSUPPORTED, "no energy check kernel of this width");
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->e_shmem));
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dws};
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->e_shmem, 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(du, ddu, (size_t)N * (n + 1) * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

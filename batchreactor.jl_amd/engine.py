@@ -52,6 +52,22 @@ def phase_grid(t_ign, tau, tf):
         return np.where(p <= tf[:, None], p, np.nan)
 
 
+def energy_mode(energy):
+    """The energy argument of the integrate calls as br_opts.energy: None / False / 0 = the temperature is
+    prescribed (isothermal or a programme), "adiabatic" (or 1) = adiabatic constant-volume reactors, T a state
+    component (BR_ENERGY_ADIABATIC_V). Other integers pass through for the library to reject; any other
+    value raises ValueError."""
+    if energy is None or energy is False:
+        return 0
+    if isinstance(energy, str):
+        if energy == "adiabatic":
+            return _lib.ENERGY_ADIABATIC_V
+        raise ValueError(f"energy must be None or 'adiabatic', got {energy!r}")
+    if isinstance(energy, (int, np.integer)):
+        return int(energy)
+    raise ValueError(f"energy must be None or 'adiabatic', got {energy!r}")
+
+
 def rate_mult_table(rate_mult, rate_mult_row, N, nr):
     """The rate_mult / rate_mult_row arguments of the integrate calls as C arrays (br_opts.rate_mult):
     rate_mult [nmult, nr] float64 with nr = nrg + nrs (gas reactions in mechanism order, then surface
@@ -235,6 +251,18 @@ class Engine:
                                                  _lib.dptr(du), _lib.dptr(J)))
         return du, J
 
+    def energy_eval(self, T, u, rate_mult=None, rate_mult_row=None):
+        """du [N, ng + 1] = (du_0 .. du_{ng-1}, dT/dt) as the energy instance of the wavefront integrator evaluates
+        it at the states (u, T) (br_debug_energy_eval: its launch shape, slots and refresh path)."""
+        u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
+        N = u.shape[0]
+        T = self._arr(T, N)
+        mult, mrow = self._mult(rate_mult, rate_mult_row, N)
+        du = np.zeros((N, self.ng + 1))
+        _lib.check(_lib.lib().br_debug_energy_eval(self.h, N, _lib.dptr(T), _lib.dptr(u), 0 if mult is None else mult.shape[0],
+                                                   _lib.dptr(mult), _lib.iptr(mrow), _lib.dptr(du)))
+        return du
+
     def _mult(self, rate_mult, rate_mult_row, N):
         """rate_mult_table for this mechanism's nrg + nrs reactions; (None, None) without multipliers"""
         if rate_mult is None and rate_mult_row is None:
@@ -242,10 +270,10 @@ class Engine:
         return rate_mult_table(rate_mult, rate_mult_row, N, self.nr)
 
     def _opts(self, rtol, atol, max_steps, trace_cap=0, unstable_factor=0.0, tout=None, yout=None, dq_jacobian=False,
-              mult=None, mult_row=None, prog=None):
+              mult=None, mult_row=None, prog=None, energy=0, T_end=None, T_out=None):
         nout = 0 if tout is None else tout.shape[-1]   # tout: [nout], or [N, nout] (one row per reactor)
-        o = _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout,
-                      _lib.dptr(tout) if nout else None, _lib.dptr(yout) if nout else None, dq_jacobian=int(dq_jacobian),
+        o = _lib.Opts(rtol, atol, max_steps, self.device, 0.0, trace_cap, unstable_factor, self.ign1, nout=nout,
+                      tout=_lib.dptr(tout) if nout else None, yout=_lib.dptr(yout) if nout else None, dq_jacobian=int(dq_jacobian),
                       tout_per_reactor=int(nout > 0 and tout.ndim == 2))
         if mult is not None:   # (arrays from rate_mult_table; the caller keeps them alive for the call)
             o.nmult, o.rate_mult = mult.shape[0], _lib.dptr(mult)
@@ -254,11 +282,13 @@ class Engine:
             kt, kT, rows = prog
             o.ntprog, o.ntprog_rows = kt.shape[1], kt.shape[0]
             o.tprog_t, o.tprog_T, o.tprog_row = _lib.dptr(kt), _lib.dptr(kT), _lib.iptr(rows)
+        if energy:   # (T_end [N], T_out [N, nout]: host arrays the caller keeps alive for the call)
+            o.energy, o.T_end, o.T_out = int(energy), _lib.dptr(T_end), _lib.dptr(T_out)
         return o
 
     def integrate(self, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, trace_cap=0, tout=None,
                   unstable_factor=0.0, dq_jacobian=False, rate_mult=None, rate_mult_row=None, tprog=None,
-                  tprog_row=None):
+                  tprog_row=None, energy=None):
         """Integrate N reactors 0 -> tf. With trace_cap > 0 also returns the per-step rows
         trace[N, trace_cap+1, 2n+4] = (t, h, q, p_last, u[n], y_last[n]): u the accepted state, y_last
         and p_last the state and pressure of the step's last RHS evaluation (save_data semantics).
@@ -274,17 +304,23 @@ class Engine:
         tprog: a prescribed temperature programme T(t) (tprog.TemperatureProgram: one for all reactors, a
         sequence -- one per reactor, or the rows tprog_row [N] selects -- or a pair (t, T) of [nrows, nk]
         knot arrays). T is then not read (None is fine), u0 is the caller's state at T(0), and the run
-        uses the wavefront engine."""
+        uses the wavefront engine.
+        energy="adiabatic": adiabatic constant-volume reactors (br_opts.energy): T is T(0) and becomes a state
+        component, the stats carry "T_end" [N] and, with tout, "T_out" [N, nout]; gas-only mechanisms, the
+        wavefront engine with CVODE's DQ Jacobian (dq_jacobian is not read), not together with tprog."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
         mult, mrow = self._mult(rate_mult, rate_mult_row, N)
         prog = _tprog.table(tprog, tprog_row, N)
+        en = energy_mode(energy)
         to, _ = output_grid(tout, N)
         T = None if (T is None and prog[0] is not None) else self._arr(T, N)
         A, tf = self._arr(Asv, N), self._arr(tf, N)
         st = np.zeros((N, _lib.NSTAT))
         yo = None if to is None else np.zeros((N, to.shape[-1], self.n))
-        o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian, mult, mrow, prog)
+        Te = np.zeros(N) if en else None
+        To = np.zeros((N, to.shape[-1])) if (en and to is not None) else None
+        o = self._opts(rtol, atol, max_steps, trace_cap, unstable_factor, to, yo, dq_jacobian, mult, mrow, prog, en, Te, To)
         L = _lib.lib()
         if trace_cap > 0:
             tr = np.zeros((N, trace_cap + 1, 2 * self.n + 4))
@@ -297,20 +333,29 @@ class Engine:
         stats = {k: st[:, i] for i, k in enumerate(STAT_FIELDS)}
         if yo is not None:
             stats["yout"] = yo
+        if Te is not None:
+            stats["T_end"] = Te
+        if To is not None:
+            stats["T_out"] = To
         return (u, stats, tr) if trace_cap > 0 else (u, stats)
 
     def integrate_device(self, T_ptr, Asv_ptr, u_ptr, tf_ptr, stats_ptr, N, stream_ptr=None, rtol=1e-6,
                          atol=1e-10, max_steps=100000, tout_ptr=None, yout_ptr=None, nout=0, tout_per_reactor=False,
                          dq_jacobian=False, rate_mult=None, rate_mult_row=None, nmult=0, tprog_t=None, tprog_T=None,
-                         ntprog=0, ntprog_rows=0, tprog_row=None):
+                         ntprog=0, ntprog_rows=0, tprog_row=None, energy=None, T_end_ptr=None, T_out_ptr=None):
         """Device-resident variant: raw device pointers (e.g. torch tensor data_ptr()). Dense output
         with tout_ptr / yout_ptr / nout: device arrays tout [nout], or [N, nout] with tout_per_reactor
         (e.g. what phase_tout_device built), and yout [N, nout, n]. Rate multipliers: rate_mult is the
         device pointer of a float64 [nmult, nrg + nrs] table, rate_mult_row that of int32 [N] row indices
         (None: nmult == N, row i); the library trusts the device arrays. Temperature programmes: tprog_t /
         tprog_T the device pointers of float64 [ntprog_rows, ntprog] knot arrays, tprog_row that of int32 [N]
-        (None: ntprog_rows == N); T_ptr is then not read."""
+        (None: ntprog_rows == N); T_ptr is then not read. energy="adiabatic" as integrate: T_ptr is T(0),
+        T_end_ptr / T_out_ptr the device pointers of float64 [N] / [N, nout] outputs (either may be None)."""
         o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian)
+        o.energy = energy_mode(energy)
+        if o.energy:
+            o.T_end = C.cast(C.c_void_p(T_end_ptr), _lib.dp) if T_end_ptr else None
+            o.T_out = C.cast(C.c_void_p(T_out_ptr), _lib.dp) if T_out_ptr else None
         if tprog_t or tprog_T:
             if not (tprog_t and tprog_T) or ntprog < 1 or ntprog_rows < 1 or (not tprog_row and ntprog_rows != N):
                 raise ValueError(f"tprog needs tprog_t, tprog_T, ntprog >= 1, ntprog_rows >= 1, and ntprog_rows == N = {N} "
@@ -336,13 +381,14 @@ class Engine:
                                                C.c_void_p(stats_ptr), C.c_void_p(stream_ptr or 0)))
 
     def integrate_phase(self, T, Asv, u0, tf, tau, rtol=1e-6, atol=1e-10, max_steps=100000, dq_jacobian=False,
-                        rate_mult=None, rate_mult_row=None, tprog=None, tprog_row=None):
+                        rate_mult=None, rate_mult_row=None, tprog=None, tprog_row=None, energy=None):
         """Ignition-phase sampling (br_integrate_phase): the states at t = tau[j] * t_ign[i], two passes
         on the device from the same u0 (t_ign, then the outputs at the grid br_phase_tout_dev builds).
         Returns (u, stats) as integrate, with stats["tout"] [N, ntau] (phase_grid(t_ign, tau, tf): NaN
         where t_ign is unknown or the phase is past tf) and stats["yout"] [N, ntau, n] (rows of NaN
         entries stay 0). Needs the ignition marker species in the mechanism. rate_mult / rate_mult_row and
-        tprog / tprog_row as integrate: both passes run with them."""
+        tprog / tprog_row as integrate: both passes run with them. energy="adiabatic" as integrate: both passes
+        run with it, stats["T_end"] [N] and stats["T_out"] [N, ntau] (T at the phases) are pass 2's."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
         mult, mrow = self._mult(rate_mult, rate_mult_row, N)
@@ -355,16 +401,22 @@ class Engine:
         st = np.zeros((N, _lib.NSTAT))
         to = np.zeros((N, tau.size))
         yo = np.zeros((N, tau.size, self.n))
-        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, mult=mult, mult_row=mrow, prog=prog)
+        en = energy_mode(energy)
+        Te = np.zeros(N) if en else None
+        To = np.zeros((N, tau.size)) if en else None
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, mult=mult, mult_row=mrow, prog=prog, energy=en,
+                       T_end=Te, T_out=To)
         _lib.check(_lib.lib().br_integrate_phase(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),
                                                  C.byref(o), _lib.dptr(st), tau.size, _lib.dptr(tau), _lib.dptr(to),
                                                  _lib.dptr(yo)))
         stats = {k: st[:, i] for i, k in enumerate(STAT_FIELDS)}
         stats["tout"], stats["yout"] = to, yo
+        if en:
+            stats["T_end"], stats["T_out"] = Te, To
         return u, stats
 
     def sensitivity(self, T, Asv, u0, tf, factor=2.0, reactions=None, states=False, rtol=1e-6, atol=1e-10,
-                    max_steps=100000, dq_jacobian=False, tprog=None, tprog_row=None):
+                    max_steps=100000, dq_jacobian=False, tprog=None, tprog_row=None, energy=None):
         """Brute-force logarithmic sensitivities to the rate constants (br_sensitivity), built and reduced
         on the device: every base reactor is integrated with each selected reaction's rate times and
         over `factor`. reactions: 0-based indices (gas reactions in mechanism order, then surface
@@ -375,7 +427,8 @@ class Engine:
           "u" [N, n] and "stats": the unperturbed end states and stats, as integrate's,
           "nbad": entries set to NaN (a perturbed run failed, or has no t_ign),
           "reactions": the indices used.
-        tprog: not supported here (the library answers BR_ERR_UNSUPPORTED)."""
+        tprog: not supported here (the library answers BR_ERR_UNSUPPORTED). energy="adiabatic": the expanded
+        reactors run adiabatically from T = T(0), S_tign is the adiabatic ignition-delay sensitivity."""
         u0 = np.ascontiguousarray(np.atleast_2d(u0), dtype=np.float64)
         N = u0.shape[0]
         prog = _tprog.table(tprog, tprog_row, N)
@@ -397,7 +450,7 @@ class Engine:
         u = np.zeros((N, self.n))
         st = np.zeros((N, _lib.NSTAT))
         nbad = C.c_longlong(0)
-        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, prog=prog)
+        o = self._opts(rtol, atol, max_steps, dq_jacobian=dq_jacobian, prog=prog, energy=energy_mode(energy))
         _lib.check(_lib.lib().br_sensitivity(self.h, N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u0), _lib.dptr(tf),
                                              C.byref(o), float(factor), nsel, _lib.iptr(rx), _lib.dptr(St),
                                              _lib.dptr(Su), _lib.dptr(u), _lib.dptr(st), C.byref(nbad)))
@@ -440,12 +493,12 @@ class Engine:
 
 
 def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=100000, tout=None, rate_mult=None,
-                    rate_mult_row=None, tprog=None, tprog_row=None):
+                    rate_mult_row=None, tprog=None, tprog_row=None, energy=None):
     """br_integrate_multi: the ensemble split into contiguous slices over `engines` (one Engine per
     GPU, same mechanism), integrated concurrently; returns (u, stats) in ensemble order. tout as
     Engine.integrate: [nout], or [N, nout] for per-reactor grids (sliced with the ensemble). rate_mult /
     rate_mult_row and tprog / tprog_row as Engine.integrate (the row indices, or the rows of a dense table,
-    are sliced too)."""
+    are sliced too). energy="adiabatic" as Engine.integrate: stats carry "T_end" and, with tout, "T_out"."""
     e0 = engines[0]
     u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
     N = u.shape[0]
@@ -456,7 +509,10 @@ def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=10
     A, tf = e0._arr(Asv, N), e0._arr(tf, N)
     st = np.zeros((N, _lib.NSTAT))
     yo = None if to is None else np.zeros((N, to.shape[-1], e0.n))
-    o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo, mult=mult, mult_row=mrow, prog=prog)
+    en = energy_mode(energy)
+    Te = np.zeros(N) if en else None
+    To = np.zeros((N, to.shape[-1])) if (en and to is not None) else None
+    o = e0._opts(rtol, atol, max_steps, 0, 0.0, to, yo, mult=mult, mult_row=mrow, prog=prog, energy=en, T_end=Te, T_out=To)
     L = _lib.lib()
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     _lib.check(L.br_integrate_multi(hs, len(engines), N, _lib.dptr(T), _lib.dptr(A), _lib.dptr(u), _lib.dptr(tf),
@@ -464,4 +520,8 @@ def integrate_multi(engines, T, Asv, u0, tf, rtol=1e-6, atol=1e-10, max_steps=10
     stats = {k: st[:, i] for i, k in enumerate(STAT_FIELDS)}
     if yo is not None:
         stats["yout"] = yo
+    if Te is not None:
+        stats["T_end"] = Te
+    if To is not None:
+        stats["T_out"] = To
     return u, stats

@@ -457,3 +457,39 @@ class Mechanism:
         y = u[..., :self.ng] / np.sum(u[..., :self.ng], axis=-1, keepdims=True)
         t = y / self.molwt
         return t / np.sum(t, axis=-1, keepdims=True)
+
+    # ---- thermodynamics of an energy run (br_opts.energy; the CPU statement of the model in include/brhip.h) ----
+    @staticmethod
+    def clamp_T(T):
+        """Tc = T < 200 ? 200 : (T > 6000 ? 6000 : T); a NaN passes through."""
+        T = np.asarray(T, float)
+        return np.where(T < 200.0, 200.0, np.where(T > 6000.0, 6000.0, T))
+
+    def thermo_e_cv(self, T):
+        """(e[ng], cv[ng]) at temperature T (a scalar; [..., ng] for an array of temperatures):
+        e_k = (h_k/RT - 1) R Tc [J/mol] and cv_k = (cp_k/R - 1) R [J/mol/K], h_k/RT and cp_k/R from species
+        k's NASA-7 row, the low range when Tc < Tmid, else the high one (the branch rule of g/RT), Tc the
+        clamped T (clamp_T). Plain numpy."""
+        Tc = self.clamp_T(T)[..., None]
+        tmid, hi, lo = self.nasa[:, 0], self.nasa[:, 1:8], self.nasa[:, 8:15]
+        a = np.where((Tc < tmid)[..., None], lo, hi)
+        T1 = Tc
+        hrt = (a[..., 0] + a[..., 1] * T1 / 2 + a[..., 2] * T1 * T1 / 3 + a[..., 3] * T1 * T1 * T1 / 4
+               + a[..., 4] * T1 * T1 * T1 * T1 / 5 + a[..., 5] / T1)
+        cpr = a[..., 0] + a[..., 1] * T1 + a[..., 2] * T1 * T1 + a[..., 3] * T1 * T1 * T1 + a[..., 4] * T1 * T1 * T1 * T1
+        return (hrt - 1.0) * (R_GAS * T1), (cpr - 1.0) * R_GAS
+
+    def internal_energy(self, u, T):
+        """E = sum_k c_k e_k(T) [J/m3] of the gas state u (u_k = rho Y_k, c_k = u_k / M_k) at T; u [..., >= ng]
+        with T of the leading shape. An adiabatic constant-volume run conserves it."""
+        u = np.asarray(u, float)
+        e, _ = self.thermo_e_cv(T)
+        return np.sum(u[..., :self.ng] / self.molwt * e, axis=-1)
+
+    def energy_rhs(self, du_species, u, T):
+        """dT/dt = - sum_k e_k w_k / sum_k c_k cv_k of one reactor, w_k = du_k / M_k from the species RHS
+        du_species (evaluated at clamp_T(T)), c_k = u_k / M_k."""
+        e, cv = self.thermo_e_cv(float(T))
+        w = np.asarray(du_species, float)[:self.ng] / self.molwt
+        c = np.asarray(u, float)[:self.ng] / self.molwt
+        return -float(np.sum(e * w)) / float(np.sum(c * cv))

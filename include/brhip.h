@@ -53,6 +53,9 @@ extern "C" {
 #define BR_CONV_TROE_C4      16   /* Troe c = -4.0 - 0.67 log10 Fcent                       */
 #define BR_CONV_REFERENCE    (BR_CONV_KC_UNIT_SLIP | BR_CONV_FALLOFF_XM | BR_CONV_TROE_C4)
 
+/* br_opts.energy */
+#define BR_ENERGY_ADIABATIC_V 1   /* adiabatic, constant volume: T is a state component */
+
 typedef struct br_mech br_mech;
 
 typedef struct br_mech_desc {
@@ -99,6 +102,38 @@ typedef struct br_opts {
     int ignition_species;     /* 1-based gas species index k+1 whose max dX_k/dt over the accepted
                                  steps marks ignition (br_stats.t_ign; OH for the reference's
                                  ignition marker); 0 = not tracked                          */
+    int energy;               /* 0 (default): the reactor stays at its T[i] (or follows its programme).
+                                 BR_ENERGY_ADIABATIC_V: adiabatic constant-volume reactor. The state of
+                                 reactor i is (u_0 .. u_{ng-1}, T) with u_k = rho Y_k; the T argument of the
+                                 entry point is T(0). The species equations are the isothermal du_k/dt
+                                 evaluated at the current T (RT in the diagnosed pressure, every T-only
+                                 constant with the reactor's rate multipliers), and
+                                     dT/dt = - ( sum_k e_k(Tc) w_k ) / ( sum_k c_k cv_k(Tc) ),
+                                     c_k = u_k / M_k,   w_k = (du_k/dt) / M_k,
+                                     e_k = (h_k/RT - 1) R Tc,   cv_k = (cp_k/R - 1) R,
+                                 h_k/RT and cp_k/R from species k's NASA-7 row (the low range when
+                                 T < Tmid, else the high one, as for g/RT). w_k is taken from the RHS's own
+                                 du_k, so the integrated system conserves E = sum_k c_k e_k(T) identically,
+                                 whatever conv bits are set. Tc = T < 200 ? 200 : (T > 6000 ? 6000 : T), a
+                                 NaN passes through: everything that depends on temperature (constants,
+                                 thermo, RT) is evaluated at Tc, so a Newton iterate outside the fits
+                                 cannot produce a NaN from log. The NaN-state check covers the T component;
+                                 the opt-in unstable_factor test looks at the species only. Error weight of
+                                 T: 1 / (rtol |T| + atol), as for any other component. Gas-only mechanisms
+                                 with ng + 1 <= 56 (else BR_ERR_UNSUPPORTED). An energy run always uses the
+                                 wavefront engine and CVODE's DQ Jacobian over ng + 1 columns: dq_jacobian
+                                 is not read, nfe_dq == nje * (ng + 1). Rate multipliers, tout,
+                                 tout_per_reactor, the ignition marker, hmax and max_steps behave as in an
+                                 isothermal run. Not together with ntprog (BR_ERR_INPUT), any other value
+                                 is BR_ERR_INPUT; br_integrate_traced answers BR_ERR_UNSUPPORTED (the trace
+                                 row has no T column). u, yout and their shapes do not change          */
+    double* T_end;            /* [N] out, or NULL: T at t_end (the last accepted state's on failure). Host
+                                 memory for the host entry points, device memory for br_integrate_dev    */
+    double* T_out;            /* [N][nout] out, or NULL: T at the dense-output times; entries are left
+                                 untouched where the rows of yout are. (These three sit between
+                                 ignition_species and nout: the fields from yout's successor ntprog to
+                                 tout_per_reactor keep their order, as the bindings' tests pin them; a caller
+                                 built against the earlier header must be rebuilt, br_version() 230)     */
     int nout;                 /* dense output: number of output times (0 = none)            */
     const double* tout;       /* [nout] ascending output times, shared by all reactors (or
                                  [N][nout], one row per reactor, with tout_per_reactor); the
@@ -137,7 +172,7 @@ typedef struct br_opts {
                                  tout_per_reactor stay the struct's tail, in their order; a caller built
                                  against the earlier header must be rebuilt, and br_version() 220 tells
                                  the layouts apart)                                                   */
-    int dq_jacobian;          /* 1: CVODE's dense difference-quotient Jacobian (cvLsDenseDQJac:
+    int dq_jacobian;         /* 1: CVODE's dense difference-quotient Jacobian (cvLsDenseDQJac:
                                  the reference's CVODE_BDF() setting, src/BatchReactor.jl:140,
                                  :204), n extra RHS per Jacobian, in every engine (lane,
                                  group, wavefront); 0 (default): the analytic Jacobian       */
@@ -302,7 +337,9 @@ int br_phase_tout_dev(int N, br_stats* dstats /*read only*/, int ntau, const dou
  * ascending, positive and finite. Needs opts->ignition_species != 0 (else BR_ERR_INPUT);
  * opts->nout / tout / yout / tout_per_reactor are ignored. u (in: u0, out: u(tf)) and stats are pass
  * 2's, equal to a plain br_integrate's. tout[N][ntau] receives the grid (NaN = no output: t_ign
- * unknown or tau[j] t_ign[i] > tf[i]); yout[N][ntau][n] rows of NaN entries are left untouched. */
+ * unknown or tau[j] t_ign[i] > tf[i]); yout[N][ntau][n] rows of NaN entries are left untouched. With
+ * opts->energy both passes run with it; opts->T_end [N] and opts->T_out [N][ntau] (T at the phases, entries of
+ * NaN times left untouched) are pass 2's. */
 int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, double* u, const double* tf,
                        const br_opts* opts, br_stats* stats, int ntau, const double* tau,
                        double* tout /*[N][ntau] out*/, double* yout /*[N][ntau][n] out*/);
@@ -318,7 +355,9 @@ int br_integrate_phase(br_mech* m, int N, const double* T, const double* Asv, do
  * budget (env BRHIP_SENS_CHUNK = base reactors per launch overrides it; the results do not depend on
  * it), and reduced there: only S, the unperturbed end states u[N][n] and their stats cross to the host.
  * An entry is NaN when either perturbed run failed, S_tign also when either has no t_ign; *nbad counts
- * the NaN entries written. opts->rate_mult must be unset; the output fields of opts are ignored. Host
+ * the NaN entries written. opts->rate_mult must be unset; the output fields of opts are ignored. With
+ * opts->energy the expanded reactors run adiabatically (T_end and T_out are ignored) and S_tign is the
+ * adiabatic ignition-delay sensitivity. Host
  * memory throughout; S_tign, S_u, u, stats and nbad may each be NULL. */
 int br_sensitivity(br_mech* m, int N, const double* T, const double* Asv, const double* u0, const double* tf,
                    const br_opts* opts, double factor, int nsel, const int* rxn /*[nsel] or NULL = all*/,
@@ -371,6 +410,15 @@ int br_debug_lane_lu_solve(int nm, int N, int n, const double* J, const double* 
  * temperature-programme run refreshes them. Multipliers as br_debug_lane_eval. Asv may be NULL (1.0). */
 int br_debug_wave_eval(br_mech* m, int N, const double* T, const double* Asv, const double* u, const double* T_prev,
                        int nmult, const double* rate_mult, const int* rate_mult_row, double* du, double* J);
+
+/* energy-run check (tests): the right-hand side of the adiabatic instances of k_integrate (br_opts.energy),
+ * through their own device functions: du[i] = (du_0 .. du_{ng-1}, dT/dt) at state (u[i], T[i]). The
+ * integrator's launch shape, LDS block and workspace slot (one workgroup up to N = 4 rpb reactors, two
+ * above, as br_debug_wave_eval), and the refresh path: the constants and the lanes' e_k, cv_k are first built
+ * at another temperature, then rebuilt at T in the live slot. T outside [200, 6000] is clamped as in a run.
+ * Multipliers as br_debug_lane_eval. BR_ERR_UNSUPPORTED as an energy run. */
+int br_debug_energy_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
+                         const int* rate_mult_row, double* du /*[N][ng+1]*/);
 
 /* temperature-programme check (tests): Tout[i][k] = T(t[i][k]) of reactor i's programme, through the
  * device evaluator the integrator calls (one thread per reactor; consecutive times of a row reuse the

@@ -50,6 +50,9 @@ struct BrOpts
     trace_cap::Cint
     unstable_factor::Float64
     ignition_species::Cint      # 1-based gas species index (OH) for br_stats.t_ign; 0 = off
+    energy::Cint                # 0: T prescribed; 1 (ENERGY_ADIABATIC_V): adiabatic constant-volume reactor, T a state component
+    T_end::Ptr{Float64}         # [N] out: T at t_end, or C_NULL
+    T_out::Ptr{Float64}         # [nout x N] out: T at the dense-output times, or C_NULL
     nout::Cint
     tout::Ptr{Float64}          # [nout] ascending output times ([nout x N] with tout_per_reactor)
     yout::Ptr{Float64}          # [N][nout][n]
@@ -64,18 +67,23 @@ struct BrOpts
     rate_mult_row::Ptr{Cint}    # [N] 0-based row of reactor i, or C_NULL: nmult == N, row i
     tout_per_reactor::Cint      # 1: tout is [nout x N], column i reactor i's own ascending grid (NaN = no output, trailing only)
 end
-# The sixteen options without a temperature programme, in the struct's order: the positional form callers
-# had before the programme fields went in between yout and dq_jacobian
+const ENERGY_ADIABATIC_V = Cint(1)   # br_opts.energy
+# The sixteen options without a temperature programme or an energy equation, in the struct's order: the
+# positional form callers had before the programme fields went in between yout and dq_jacobian and the energy
+# fields between ignition_species and nout
 BrOpts(rtol, atol, max_steps, device, hmax, trace_cap, unstable_factor, ignition_species, nout, tout, yout,
        dq_jacobian, nmult, rate_mult, rate_mult_row, tout_per_reactor) =
-    BrOpts(rtol, atol, max_steps, device, hmax, trace_cap, unstable_factor, ignition_species, nout, tout, yout,
+    BrOpts(rtol, atol, max_steps, device, hmax, trace_cap, unstable_factor, ignition_species, Cint(0), C_NULL, C_NULL,
+           nout, tout, yout,
            Cint(0), C_NULL, C_NULL, Cint(0), C_NULL, dq_jacobian, nmult, rate_mult, rate_mult_row, tout_per_reactor)
 # a copy of `o` with the named fields replaced
 set_fields(o::BrOpts; kw...) =
     BrOpts((haskey(kw, f) ? kw[f] : getfield(o, f) for f in fieldnames(BrOpts))...)
 # `o` with the temperature programme of `from`
+# (... and its energy fields: what the sixteen-option form leaves out travels together)
 keep_tprog(o::BrOpts, from::BrOpts) = set_fields(o; ntprog=from.ntprog, tprog_t=from.tprog_t, tprog_T=from.tprog_T,
-                                                 ntprog_rows=from.ntprog_rows, tprog_row=from.tprog_row)
+                                                 ntprog_rows=from.ntprog_rows, tprog_row=from.tprog_row,
+                                                 energy=from.energy, T_end=from.T_end, T_out=from.T_out)
 # dq_jacobian=true selects CVODE's difference-quotient Jacobian, the reference's CVODE_BDF() setting
 # (src/BatchReactor.jl:140,:204); the default is the analytic Jacobian
 BrOpts(; rtol=1e-6, atol=1e-10, max_steps=100_000, device=0, hmax=0.0, unstable_factor=0.0, ignition_species=0,
@@ -100,6 +108,14 @@ function with_tprog(o::BrOpts, t::Matrix{Float64}, Tk::Matrix{Float64}, rows::Un
     size(t) == size(Tk) || error("tprog: t and T must have the same size")
     return set_fields(o; ntprog=Cint(size(t, 1)), tprog_t=pointer(t), tprog_T=pointer(Tk), ntprog_rows=Cint(size(t, 2)),
                       tprog_row=(rows === nothing ? Ptr{Cint}(C_NULL) : pointer(rows)))
+end
+# the same options for adiabatic constant-volume reactors (br_opts.energy = ENERGY_ADIABATIC_V): the T argument of
+# the integrate call is T(0) and T becomes a state component. `T_end` (N) and `T_out` (nout x N, with outputs)
+# receive T at the end and at the output times, or nothing. Gas-only mechanisms; not together with with_tprog.
+# The caller keeps the arrays alive (GC.@preserve).
+function with_energy(o::BrOpts; T_end::Union{Nothing,Vector{Float64}}=nothing, T_out::Union{Nothing,Matrix{Float64}}=nothing)
+    return set_fields(o; energy=ENERGY_ADIABATIC_V, T_end=(T_end === nothing ? Ptr{Float64}(C_NULL) : pointer(T_end)),
+                      T_out=(T_out === nothing ? Ptr{Float64}(C_NULL) : pointer(T_out)))
 end
 
 # br_stats rows of the [NSTAT x N] matrix returned below
@@ -662,7 +678,7 @@ function batch_reactor(input_file::AbstractString, lib_dir::AbstractString, user
 end
 
 export batch_reactor, batch_reactor_ensemble, compile_mechanism, read_batch_xml, DeviceMech, Chemistry,
-       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!, with_rate_mult, with_tprog, sensitivity,
+       UserDefinedState, BrOpts, retcode_symbol, integrate_host, integrate_phase!, with_rate_mult, with_tprog, with_energy, sensitivity,
        ignition_sensitivity
 
 end # module
