@@ -55,7 +55,8 @@ EXPORTS = ["br_version", "br_last_error", "br_device_count", "br_mech_create", "
            "br_host_mech_species", "br_host_mech_theta0", "br_host_mech_free", "br_mech_compile", "br_read_batch_xml",
            "br_integrate_host", "br_phase_tout_dev", "br_integrate_phase", "br_debug_group_eval",
            "br_debug_group_lu_solve", "br_sensitivity", "br_debug_tprog_eval", "br_debug_lane_eval",
-           "br_debug_lane_lu_solve", "br_debug_wave_eval", "br_debug_energy_eval"]
+           "br_debug_lane_lu_solve", "br_debug_wave_eval", "br_debug_energy_eval", "br_mech_energy_launch_info",
+           "br_debug_group_energy_eval"]
 
 # br_integrate_host callbacks: int f(void* user, double t, const double* u, double* du);
 # void cb(void* user, double t, const double* u)
@@ -110,6 +111,10 @@ def lib():
     L.br_debug_wave_eval.restype = C.c_int
     L.br_debug_energy_eval.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, ip, dp]
     L.br_debug_energy_eval.restype = C.c_int
+    L.br_mech_energy_launch_info.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_longlong), ip]
+    L.br_mech_energy_launch_info.restype = C.c_int
+    L.br_debug_group_energy_eval.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, ip, dp]
+    L.br_debug_group_energy_eval.restype = C.c_int
     cs = C.c_char_p
     L.br_mech_parse.argtypes = [cs, cs, cs, cs, C.c_int, C.POINTER(vp)]
     L.br_host_mech_desc.argtypes = [vp, C.POINTER(MechDesc)]

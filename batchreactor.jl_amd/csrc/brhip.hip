@@ -25,10 +25,10 @@
 namespace {
 
 #include "brhip_lane.hpp"   // one reactor per lane (small gas mechanisms)
+#include "brhip_energy.hpp"  // adiabatic constant-volume reactors: T as component ng of the energy instances
 #include "brhip_group.hpp"   // group engines: 4 / 2 reactors per wave (16- / 32-lane groups, n <= 32)
 #include "brhip_sens.hpp"    // rate-multiplier block, br_sensitivity's expansion and reduction kernels
 #include "brhip_tprog.hpp"   // temperature programmes T(t): the launch's block and the evaluator
-#include "brhip_energy.hpp"  // adiabatic constant-volume reactors: T as component ng of the energy instances
 
 // ------------------------------------------------------------------------------------
 // the integrator kernel: one reactor per 64-lane wavefront, `rpb` reactors per workgroup
@@ -478,6 +478,9 @@ static const void* grp_instance(int gl, int nm, F f) {
 static const void* grp_kernel(int gl, int nm) {
     return grp_instance(gl, nm, [](auto g, auto w) { return (const void*)k_group<g(), w()>; });
 }
+static const void* grp_energy_kernel(int gl, int nm) {   // ... of an adiabatic run, (gl, nm) from ng + 1
+    return grp_instance(gl, nm, [](auto g, auto w) { return (const void*)k_group<g(), w(), true>; });
+}
 static const void* wave_kernel(int nmax) {   // one reactor per wavefront
     return nmax == 16 ? (const void*)k_integrate<16> : nmax == 32 ? (const void*)k_integrate<32>
          : nmax == 56 ? (const void*)k_integrate<56> : nmax == 64 ? (const void*)k_integrate<64>
@@ -546,6 +549,11 @@ struct br_mech {
     // first such run (energy_shape); e_nmax = 0: not looked for yet
     int e_nmax = 0, e_rpb = 0, e_waves_per_cu = 0;
     size_t e_shmem = 0;
+    // ... on a group engine (k_group<ge_gl, ge_nm, true>, (ge_gl, ge_nm) from ng + 1): its own LDS block, slot size
+    // and occupancy, found at the first look (group_energy_shape); ge_state 0: not looked for yet, 1: has one,
+    // -1: has none (surface species, ng + 1 > 32, too many efficiency sets, or the LDS)
+    int ge_state = 0, ge_gl = 0, ge_nm = 0, ge_blocks = 0;
+    size_t ge_shmem = 0;
     MultBlock* mult_hdr = nullptr;   // the 32 bytes in front of the g_par table (br_opts.rate_mult; brhip_device.hpp)
 };
 
@@ -593,7 +601,7 @@ struct Stage {
 
 extern "C" {
 
-int br_version(void) { return 230; }   // 230: br_opts grew (energy, T_end, T_out between tprog_row and dq_jacobian)
+int br_version(void) { return 231; }   // 231: br_mech_energy_launch_info, br_debug_group_energy_eval (br_opts as in 230)
 const char* br_last_error(void) { return g_err.c_str(); }
 int br_device_count(void) {
     int c = 0;
@@ -998,6 +1006,40 @@ static int energy_shape(br_mech* m) {
     return 0;
 }
 
+// the group energy instance of a mechanism (brhip_group.hpp, k_group<GL, NM, true>): (GL, NM) from nsys = ng + 1,
+// one shape up from the isothermal instance where ng = 9, 16 or 24; its LDS block and resident workgroups from the
+// occupancy calculator on that kernel, kept in the handle. Returns whether the mechanism has one.
+static bool group_energy_shape(br_mech* m) {
+    if (m->ge_state) return m->ge_state > 0;
+    m->ge_state = -1;
+    const int nsys = m->ng + 1;
+    if (m->ns > 0 || nsys > 32 || m->dm.nset > grp::MAX_SETS) return false;
+    const int gl = nsys <= 16 ? 16 : 32, nm = nsys <= 9 ? 9 : (nsys <= 16 ? 16 : (nsys <= 24 ? 24 : 32));
+    const void* gfn = grp_energy_kernel(gl, nm);
+    const size_t shmem = (size_t)m->dm.img_bytes + (size_t)BR_QWPB * (64 / gl) * grp::block_bytes(gl, nm, m->nrg, m->dm.nfo, 0);
+    int nb = 0;
+    if (shmem > LDS_PER_CU || hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gfn, 64 * BR_QWPB, shmem) != hipSuccess || nb <= 0)
+        return false;
+    nb = std::min(nb, (int)(LDS_PER_CU / ((shmem + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
+    m->ge_gl = gl; m->ge_nm = nm; m->ge_shmem = shmem;
+    m->ge_blocks = nb * std::max(m->ncu, 1);
+    m->ge_state = 1;
+    return true;
+}
+// engine of an energy run (codes of br_mech_engine): the group energy instance when BRHIP_ENGINE asks for the
+// group width ng + 1 selects (quad: ng + 1 <= 16, pair: 16 < ng + 1 <= 32) and the mechanism has one; in every
+// other case -- BRHIP_ENGINE unset, wave, lane, the other width, an ineligible mechanism -- 0, the wavefront
+// energy instance
+static int pick_energy_engine(br_mech* m) {
+    const char* eng = getenv("BRHIP_ENGINE");
+    if (!eng) return 0;
+    const int nsys = m->ng + 1;
+    const bool quad = strcmp(eng, "quad") == 0 && nsys <= 16, pair = strcmp(eng, "pair") == 0 && nsys > 16 && nsys <= 32;
+    if (!(quad || pair) || !group_energy_shape(m)) return 0;
+    return -(100 * m->ge_gl + m->ge_nm);
+}
+
 // the kernel options of a run: br_opts with its defaults filled in (no work list, no deferral)
 static KOpts make_kopts(const br_mech* m, const br_opts* opts, bool traced) {
     KOpts o;
@@ -1057,6 +1099,29 @@ static int launch_wave_energy(br_mech* m, const DevMech& dm, int N, int nwg, con
     return 0;
 }
 
+int br_mech_energy_launch_info(br_mech* m, int* engine, int* rpb, int* waves_per_cu, long long* lds_bytes, int* resident) {
+    if (!m) return fail(BR_ERR_INPUT, "null mechanism");
+    HIPCHK(hipSetDevice(m->device));
+    if (const int rc = energy_shape(m)) return rc;
+    const int e = pick_energy_engine(m);
+    const int ncu = m->ncu > 0 ? m->ncu : 1;
+    // wavefront energy instance: e_rpb reactors (waves) per workgroup, the persistent grid of integrate_dev
+    int r = m->e_rpb, w = m->e_waves_per_cu, res = ncu * (m->e_waves_per_cu / m->e_rpb) * m->e_rpb;
+    long long l = (long long)m->e_shmem;
+    if (e < 0) {   // group energy instance: BR_QWPB waves per workgroup, 64 / GL reactors per wave
+        r = BR_QWPB * (64 / m->ge_gl);
+        w = m->ge_blocks / ncu * BR_QWPB;
+        l = (long long)m->ge_shmem;
+        res = m->ge_blocks * r;
+    }
+    if (engine) *engine = e;
+    if (rpb) *rpb = r;
+    if (waves_per_cu) *waves_per_cu = w;
+    if (lds_bytes) *lds_bytes = l;
+    if (resident) *resident = res;
+    return 0;
+}
+
 static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv, double* du, const double* dtf,
                          const br_opts* opts, br_stats* dstats, void* stream, double* trace) {
     if (const int rc = energy_request(opts)) return rc;   // (before the handle is looked at, as the programme checks)
@@ -1081,8 +1146,32 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
         dm.g_par = reinterpret_cast<const double*>(reinterpret_cast<size_t>(dm.g_par) | 1u);
     }
     if (energy) {
-        // the wavefront engine's persistent grid (below) on the energy instance and its shape, CVODE's DQ Jacobian
-        o.dq_jac = 1;
+        o.dq_jac = 1;   // CVODE's DQ Jacobian, in either engine
+        if (pick_energy_engine(m) < 0) {
+            // the group launch (below) on the energy instance and its shape: persistent grid over the resident
+            // workgroups, reactors from a work counter, m->qws sized by the energy instance's slot
+            const int GL = m->ge_gl;
+            const int gpb = BR_QWPB * (64 / GL);
+            const int blocks = std::max(1, std::min((N + gpb - 1) / gpb, m->ge_blocks));
+            HIPCHK(m->qws.ensure((size_t)blocks * gpb * grp::slot_doubles(GL, m->nrg) * sizeof(double)));
+            HIPCHK(m->queue.ensure((2 + DEFER_CAP) * sizeof(int)));
+            HIPCHK(hipMemsetAsync(m->queue.p, 0, 2 * sizeof(int), s));
+            KOptsEnergy oe;
+            static_cast<KOpts&>(oe) = o;
+            oe.work = m->queue.as<int>();
+            oe.T_end = opts->T_end;
+            oe.T_out = o.nout ? opts->T_out : nullptr;
+            const void* gfn = grp_energy_kernel(GL, m->ge_nm);
+            HIPCHK(hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->ge_shmem));
+            HIPCHK(hipEventRecord(m->ev0, s));
+            double* qws = m->qws.as<double>();
+            void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf, (void*)&oe, (void*)&dstats, (void*)&qws};
+            HIPCHK(hipLaunchKernel(gfn, dim3(blocks), dim3(64 * BR_QWPB), args, m->ge_shmem, s));
+            HIPCHK(hipEventRecord(m->ev1, s));
+            m->ev_recorded = true;
+            return 0;
+        }
+        // the wavefront engine's persistent grid (below) on the energy instance and its shape
         const int rpb = m->e_rpb;
         const char* st_env = getenv("BRHIP_STATIC");
         const bool dyn = !(st_env && atoi(st_env) == 1) && m->ncu > 0 && m->e_waves_per_cu >= rpb;

@@ -1,5 +1,5 @@
 // brhip_debug.hpp -- test and diagnostic kernels (k_lu_check*, k_group_eval, k_group_lu, k_lane_eval,
-// k_lane_lu, k_wave_eval) and their extern "C" entry points (br_debug_*, br_diag_sub). Included at the
+// k_lane_lu, k_wave_eval, k_energy_eval, k_group_energy_eval) and their extern "C" entry points (br_debug_*, br_diag_sub). Included at the
 // end of brhip.hip: they use its error helpers and br_mech.
 // ------------------------------------------------------------------------------------
 // dense-solver check: factor (I - gamma*J) with the row-per-lane LU of the integrator and
@@ -461,6 +461,39 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) void k_energy_eval(DevMech M,
         if (lane <= n) DU[(size_t)rid * (n + 1) + lane] = f[0];
     }
 }
+
+// ... of the group engine's energy instances (k_group<GL, NM, true>): their device functions (energy_tclamp,
+// g_init_tconst<GL> with the reactor's multiplier row, energy_thermo, g_rhs<GL>, energy_tdot<GL>) in k_group's
+// workgroup shape, LDS blocks and global slots. Reactors slot, slot + G, ... one after another in the group's
+// block and slot; two legs per reactor as above, the second through the refresh sequence of k_group (wave_sync,
+// g_init_tconst in the live slot), under the same group divergence.
+template <int GL, int NM>
+__global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL == 16 ? BR_QWPE : BR_QWPE32))) void k_group_energy_eval(
+    DevMech M, int N, const double* __restrict__ Tv, const double* __restrict__ U, double* __restrict__ DU,
+    double* __restrict__ Jws) {
+    GRP_CONTEXT(M, Jws);
+    (void)asv_fixed; (void)jst; (void)jld;                              // (gas-only, no Jacobian here)
+    const int G = (int)gridDim.x * (BR_QWPB * GPW);
+    for (int rid = slot;; rid += G) {
+        if (__ballot(rid < N) == 0) break;
+        if (rid < N) {                                                  // (idle groups wait, as k_group's)
+            const double y = gl < n ? U[(size_t)rid * n + gl] : (gl == n ? Tv[rid] : 0.0);
+            double T = 0.0, ek = 0.0, cvk = 0.0, fv = 0.0;
+#pragma unroll 1
+            for (int leg = 0; leg < 2; ++leg) {
+                T = energy_tclamp(gbcast<GL>(y, n) + (leg == 0 ? 150.0 : 0.0));
+                if (leg) wave_sync();
+                g_init_tconst<GL>(tb, sp, kd, fod, skd, T, gl, rid);
+                energy_thermo(gl, n, T, ek, cvk);
+                fv = g_rhs<GL>(tb, sp, kd, fod, skd, T, 1.0, 1.0, y, gl, p_last);
+                const double Td = energy_tdot<GL>(tb, gl, n, y, fv, ek, cvk);
+                if (gl == n) fv = Td;
+            }
+            if (gl <= n) DU[(size_t)rid * (n + 1) + gl] = fv;
+            wave_sync();
+        }
+    }
+}
 }  // namespace
 
 static const void* energy_eval_kernel(int nmax) {
@@ -607,6 +640,34 @@ extern "C" int br_debug_energy_eval(br_mech* m, int N, const double* T, const do
     HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->e_shmem));
     void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dws};
     HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->e_shmem, 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(du, ddu, (size_t)N * (n + 1) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int br_debug_group_energy_eval(br_mech* m, int N, const double* T, const double* u, int nmult,
+                                          const double* rate_mult, const int* rate_mult_row, double* du) {
+    if (!m || N <= 0 || !T || !u || !du) return fail(BR_ERR_INPUT, "bad argument");
+    HIPCHK(hipSetDevice(m->device));
+    if (!group_energy_shape(m))
+        return fail(BR_ERR_UNSUPPORTED, "mechanism has no group energy instance (gas-only, ng + 1 <= 32, <= 32 efficiency sets)");
+    const int n = m->n, GL = m->ge_gl, NM = m->ge_nm;
+    const int gpb = BR_QWPB * (64 / GL);
+    const int blocks = std::min(2, (N + gpb - 1) / gpb);                // small fixed grid: the groups reuse their slots
+    double *dT, *du_, *ddu, *dws;
+    DevScratch S;
+    DevMech dm = m->dm;
+    if (const int rc = debug_stage_mult(m, N, nmult, rate_mult, rate_mult_row, S, dm)) return rc;
+    HIPCHK(S.alloc(&dT, (size_t)N * 8));
+    HIPCHK(S.alloc(&du_, (size_t)N * n * 8));
+    HIPCHK(S.alloc(&ddu, (size_t)N * (n + 1) * 8));
+    HIPCHK(S.alloc(&dws, (size_t)blocks * gpb * grp::slot_doubles(GL, m->nrg) * 8));
+    HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
+    const void* fn = grp_instance(GL, NM, [](auto g, auto w) { return (const void*)k_group_energy_eval<g(), w()>; });
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->ge_shmem));
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dws};
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * BR_QWPB), args, m->ge_shmem, 0));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * (n + 1) * 8, hipMemcpyDeviceToHost));
     return 0;

@@ -7,6 +7,8 @@
 // lane ng. The chemistry keeps M.n = ng (rhs<1> masks lane ng out by itself); the controller, the DQ Jacobian,
 // the LU and the solve get ng + 1 through Ctl::a_n. The instance width follows ng + 1, so its LDS block and
 // launch shape are its own (energy_reactor_bytes), not those of the mechanism's isothermal instance.
+// The group engines' energy instances (k_group<GL, NM, true>, brhip_group.hpp, included after this file) use
+// KOptsEnergy, energy_tclamp, energy_thermo and energy_tdot<GL> with the lane within the group in place of `lane`.
 #pragma once
 
 // kernel options of an energy run: KOpts, then the two T outputs (device arrays, either may be nullptr)
@@ -32,6 +34,16 @@ __device__ __forceinline__ double energy_tdot(const Tab& tb, int lane, int ng, d
     const bool sp = lane < ng;
     const double w = sp ? duk / Mk : 0.0, c = sp ? uk / Mk : 0.0;
     const double num = wave_sum(ek * w), den = wave_sum(c * cvk);
+    return -(num / den);
+}
+// ... of a GW-lane group's reactor (the energy instances of k_group, brhip_group.hpp: `gl` the lane within the
+// group, T on lane ng): the same quotient with group sums in place of the wave sums
+template <int GW>
+__device__ __forceinline__ double energy_tdot(const Tab& tb, int gl, int ng, double uk, double duk, double ek, double cvk) {
+    const double Mk = tb.molwt[gl];
+    const bool sp = gl < ng;
+    const double w = sp ? duk / Mk : 0.0, c = sp ? uk / Mk : 0.0;
+    const double num = gsum<GW>(ek * w), den = gsum<GW>(c * cvk);
     return -(num / den);
 }
 

@@ -450,12 +450,21 @@ __device__ __forceinline__ int g_post_solve(LCtl* C, VA<1, GL, VS>& V, int gl, d
     double* p_last = reinterpret_cast<double*>(rbase)
 
 // the group integrator kernel: persistent grid, every group takes reactor indices from o.work
-template <int GL, int NM>
+// ENERGY: the instances of an adiabatic run (br_opts.energy; brhip_energy.hpp), GL and NM from nsys = ng + 1. They
+// take KOptsEnergy and carry T on lane ng of the group: the chemistry keeps n = ng (g_rhs returns 0 on lanes
+// >= n), the controller, the DQ column loop, g_lu and g_solve get nsys. Before an RHS whose T differs bitwise
+// from the one the group's constants were built for, the group rebuilds them (g_init_tconst, the fresh-reactor
+// path's sequence) and lane k its e_k, cv_k -- under group divergence, as the fresh branch: the groups of a wave
+// refresh at different times. The Jacobian is always CVODE's DQ one. Everything under `if constexpr (ENERGY)` is
+// theirs alone, the isothermal instances compile the source they always had.
+template <int GL, int NM, bool ENERGY = false>
 __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL == 16 ? BR_QWPE : BR_QWPE32))) void k_group(
     DevMech M, int N, const double* __restrict__ Tv, const double* __restrict__ Asvv, double* __restrict__ U,
-    const double* __restrict__ tfv, KOpts o, br_stats* __restrict__ stats, double* __restrict__ Jws) {
+    const double* __restrict__ tfv, std::conditional_t<ENERGY, KOptsEnergy, KOpts> o, br_stats* __restrict__ stats,
+    double* __restrict__ Jws) {
     static_assert(NM <= GL, "register tile wider than the group");
     GRP_CONTEXT(M, Jws);
+    const int nsys = ENERGY ? n + 1 : n;   // equations of the controller, the DQ Jacobian, the LU and the solve
     LCtl* C = (LCtl*)rbase;
     VA<1, GL, grp::vstride(GL, NM)> V{(LDbl*)(rbase + CTL_BYTES), gl};
     // this group's reactor: the first one from the work counter
@@ -465,7 +474,10 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
         return __builtin_amdgcn_ds_bpermute((int)(threadIdx.x & (64 - GL)) * 4, v);
     };
     int rid = take();
+    // T: the temperature the group's T-only constants were built for (energy run: the clamped T of the last
+    // refresh, with the lane's e_k and cv_k at it in ek, cvk; set anew with every reactor the group takes)
     double T = 0.0, Asv = 1.0, Asv_th = 1.0;
+    [[maybe_unused]] double ek = 0.0, cvk = 0.0;
     bool fresh = true;
     int dqj = -1;   // >= 0: building column dqj of the DQ Jacobian
     double a[NM];
@@ -482,21 +494,27 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 fresh = false;
                 cyc0 = wall_clock64();
                 BR_CLK_START();
-                T = Tv[rid];
+                if constexpr (ENERGY) T = energy_tclamp(Tv[rid]);
+                else T = Tv[rid];
                 Asv = Asvv ? Asvv[rid] : 1.0;
                 Asv_th = asv_fixed ? 1.0 : Asv;
                 C->a_rtol = o.rtol; C->a_atol = o.atol; C->a_hmax_inv = o.hmax_inv; C->a_ufac = o.ufac;
-                C->a_max_steps = o.max_steps; C->a_trace_cap = 0; C->a_trace = nullptr; C->a_rid = rid; C->a_n = n;
+                C->a_max_steps = o.max_steps; C->a_trace_cap = 0; C->a_rid = rid; C->a_n = nsys;
+                if constexpr (ENERGY) C->a_trace = o.T_out;   // (no trace in a group run: the slot carries T_out)
+                else C->a_trace = nullptr;
                 C->a_ign = o.ign; C->a_nout = o.nout; C->a_tout = o.tout; C->a_yout = o.yout;
                 g_init_tconst<GL>(tb, sp, kd, fod, skd, T, gl, rid);
-                const bool act = gl < n;
-                const double u0 = act ? U[(size_t)rid * n + gl] : 0.0;
+                if constexpr (ENERGY) energy_thermo(gl, n, T, ek, cvk);
+                const bool act = gl < nsys;
+                double u0;
+                if constexpr (ENERGY) u0 = gl < n ? U[(size_t)rid * n + gl] : (gl == n ? Tv[rid] : 0.0);   // lane ng: T(0)
+                else u0 = act ? U[(size_t)rid * n + gl] : 0.0;
 #pragma unroll
                 for (int j = 0; j < NVEC; ++j) V.at(j, 0) = 0.0;
                 V.at(0, 0) = u0;
                 V.at(V_Y, 0) = u0;
                 V.at(V_EWT, 0) = act ? 1.0 / (o.rtol * fabs(u0) + o.atol) : 1.0;
-                const double su = gsum<GL>(act ? fabs(u0) : 0.0);
+                const double su = gsum<GL>((ENERGY ? gl < n : act) ? fabs(u0) : 0.0);   // (the runaway limit is on the species)
 #pragma unroll
                 for (int i = 0; i < QMAX + 2; ++i) C->tau[i] = 0.0;
 #pragma unroll
@@ -523,7 +541,8 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                     // (inside rid < N: a group slot without a reactor forms no tout address)
                     int io = 0;
                     while (io < o.nout && tout_pre<true>(o.tout, (size_t)rid * o.nout + io, io, 0.0)) {
-                        if (act) o.yout[((size_t)rid * o.nout + io) * n + gl] = u0;
+                        if (gl < n) o.yout[((size_t)rid * o.nout + io) * n + gl] = u0;
+                        if constexpr (ENERGY) { if (o.T_out && gl == n) o.T_out[(size_t)rid * o.nout + io] = u0; }
                         ++io;
                     }
                     C->iout = io;
@@ -540,7 +559,24 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 if (gl == dqj) yv += inc[0];
             }
             BR_CLK(c_r);
-            const double fv = g_rhs<GL>(tb, sp, kd, fod, skd, T, Asv, Asv_th, yv, gl, p_last);
+            if constexpr (ENERGY) {
+                // T is lane ng's component of the y this RHS is evaluated at (the DQ increment included), clamped.
+                // Bitwise the cached T (the species columns of a DQ Jacobian, a Newton iterate that left T alone):
+                // the constants stand. Else the fresh branch's sequence at the new T with the reactor's multiplier
+                // row; the production sums' block, g_init_tconst's g/RT scratch, is idle between evaluations
+                const double Tc = energy_tclamp(gbcast<GL>(yv, n));
+                if (__double_as_longlong(Tc) != __double_as_longlong(T)) {
+                    T = Tc;
+                    wave_sync();
+                    g_init_tconst<GL>(tb, sp, kd, fod, skd, T, gl, rid);
+                    energy_thermo(gl, n, T, ek, cvk);
+                }
+            }
+            double fv = g_rhs<GL>(tb, sp, kd, fod, skd, T, Asv, Asv_th, yv, gl, p_last);
+            if constexpr (ENERGY) {   // f[ng] = dT/dt from the du just computed (lane ng's f was 0)
+                const double Td = energy_tdot<GL>(tb, gl, n, yv, fv, ek, cvk);
+                if (gl == n) fv = Td;
+            }
             BR_XG_AFTER_RHS();
             BR_ACC(cyc_rhs, c_r);
             double f[1] = {fv}, b[1];
@@ -554,17 +590,22 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ii * fv - ii * V.at(V_TEMP, 0)), jrs,
                                                       jvo + (unsigned)dqj * (GL * 8u), 0, 0);
                 C->nfe_dq = C->nfe_dq + 1;
-                if (++dqj < n) {
+                if (++dqj < nsys) {
                     act_code = A_RHS;
                 } else {
                     dqj = -1;
+                    if constexpr (ENERGY) {   // padding columns (the rows >= nsys of every column were stored as 0)
+#pragma unroll 1
+                        for (int j = nsys; j < NM; ++j) jst(j, 0.0);
+                    }
                     dq_newton_rhs<1, GL>(C, V, gl, b);
                     act_code = A_SETUP;
                     jac_ready = true;
                 }
             } else {
                 BR_SUB_T(pr0);
-                act_code = g_post_rhs<GL>(C, V, gl, f, b);
+                if constexpr (ENERGY) act_code = ctl_post_rhs<1, GL, grp::vstride(GL, NM), true>(C, V, gl, f, b);
+                else act_code = g_post_rhs<GL>(C, V, gl, f, b);
                 BR_SUB_ADD(3, pr0);
                 if (act_code == A_SETUP && o.dq_jac && C->newj) {
                     dq_begin<1, GL>(C, V, gl, f);
@@ -578,6 +619,7 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
 #if BR_GPRIO   // a wave with a group in its setup (the others idle) issues first
                 __builtin_amdgcn_s_setprio(BR_GPRIO);
 #endif
+                if constexpr (!ENERGY) {   // (an energy run's o.dq_jac is always set: every new J came from the DQ columns)
                 if (!jac_ready && C->newj) {                            // analytic Jacobian at y, saved
                     BR_CLK(c_j);
                     g_jac_cols<GL>(tb, sp, kd, fod, skd, T, Asv, Asv_th, gl, jst);   // column passes
@@ -586,11 +628,12 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                     BR_XG_AFTER_JAC();
                     BR_ACC(cyc_jac, c_j);
                 }
+                }
                 BR_CLK(c_l);
                 double jr[NM];
 #pragma unroll
                 for (int j = 0; j < NM; ++j) jr[j] = jld(j);
-                lu_fail = g_lu<GL, NM>(jr, C->gamma, n, gl, a, orig, dinv);
+                lu_fail = g_lu<GL, NM>(jr, C->gamma, nsys, gl, a, orig, dinv);
                 BR_XG_AFTER_LU();
                 BR_ACC(cyc_lu, c_l);
 #if BR_GPRIO
@@ -601,13 +644,14 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 BR_CLK(c_s);
                 double delta[1] = {0.0};
                 if (!lu_fail) {
-                    delta[0] = g_solve<GL, NM>(a, orig, dinv, n, gl, b[0]);
+                    delta[0] = g_solve<GL, NM>(a, orig, dinv, nsys, gl, b[0]);
                     BR_XG_AFTER_SOLVE();
                 }
                 BR_ACC(cyc_sol, c_s);
                 BR_CLK(c_p);
                 BR_SUB_T(ps_all);
-                act_code = g_post_solve<GL>(C, V, gl, delta, lu_fail);
+                if constexpr (ENERGY) act_code = ctl_post_solve<1, GL, grp::vstride(GL, NM), true>(C, V, gl, delta, lu_fail);
+                else act_code = g_post_solve<GL>(C, V, gl, delta, lu_fail);
                 BR_SUB_ADD(13, ps_all);
                 BR_ACC(cyc_ctl, c_p);
             }
@@ -615,6 +659,7 @@ __global__ __launch_bounds__(64 * BR_QWPB) __attribute__((amdgpu_waves_per_eu(GL
                 const int status = C->status;
                 const double u_out = status ? V.at(0, 0) : V.at(V_Y, 0);
                 if (gl < n) U[(size_t)rid * n + gl] = u_out;
+                if constexpr (ENERGY) { if (o.T_end && gl == n) o.T_end[rid] = u_out; }
                 if (stats && gl == 0) {
                     br_stats& s = stats[rid];
                     s.nsteps = C->nst; s.nfe = C->nfe; s.nje = C->nje; s.nsetups = C->nsetups; s.nni = C->nni;

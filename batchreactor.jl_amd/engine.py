@@ -151,6 +151,26 @@ class Engine:
         _lib.check(_lib.lib().br_mech_launch_info(self.h, C.byref(rpb), C.byref(wpc), C.byref(lds)))
         return {"reactors_per_workgroup": rpb.value, "waves_per_cu": wpc.value, "lds_bytes_per_workgroup": lds.value}
 
+    def energy_launch_info(self) -> dict:
+        """engine and launch geometry of an energy run (energy="adiabatic") of this mechanism under the current
+        BRHIP_ENGINE (br_mech_energy_launch_info): "engine" 0 = the wavefront energy instance, -(100 GL + NM) = the
+        group energy instance k_group<GL, NM, true>; reactors per workgroup, resident waves per CU, LDS bytes per
+        workgroup, and "resident", the reactors in flight at once on its persistent grid"""
+        e, rpb, wpc, lds, res = C.c_int(), C.c_int(), C.c_int(), C.c_longlong(), C.c_int()
+        _lib.check(_lib.lib().br_mech_energy_launch_info(self.h, C.byref(e), C.byref(rpb), C.byref(wpc), C.byref(lds),
+                                                         C.byref(res)))
+        return {"engine": e.value, "reactors_per_workgroup": rpb.value, "waves_per_cu": wpc.value,
+                "lds_bytes_per_workgroup": lds.value, "resident": res.value}
+
+    @property
+    def energy_kernel_name(self) -> str:
+        """the integrator kernel an energy run (energy="adiabatic") of this mechanism launches"""
+        e = self.energy_launch_info()["engine"]
+        if e < 0:
+            return f"k_group<{-e // 100}, {-e % 100}, true>"
+        nsys = self.ng + 1
+        return f"k_integrate<{16 if nsys <= 16 else 32 if nsys <= 32 else 56}, false, true>"
+
     def close(self):
         if getattr(self, "h", None):
             _lib.lib().br_mech_destroy(self.h)
@@ -263,6 +283,20 @@ class Engine:
                                                    _lib.dptr(mult), _lib.iptr(mrow), _lib.dptr(du)))
         return du
 
+    def group_energy_eval(self, T, u, rate_mult=None, rate_mult_row=None):
+        """du [N, ng + 1] as energy_eval, as the energy instance of the group engine evaluates it (br_debug_group_energy_eval:
+        k_group<GL, NM, true>'s device functions, LDS blocks, global slots and refresh path; does not read
+        BRHIP_ENGINE). The library answers -30 when the mechanism has no such instance."""
+        u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
+        N = u.shape[0]
+        T = self._arr(T, N)
+        mult, mrow = self._mult(rate_mult, rate_mult_row, N)
+        du = np.zeros((N, self.ng + 1))
+        _lib.check(_lib.lib().br_debug_group_energy_eval(self.h, N, _lib.dptr(T), _lib.dptr(u),
+                                                         0 if mult is None else mult.shape[0], _lib.dptr(mult), _lib.iptr(mrow),
+                                                         _lib.dptr(du)))
+        return du
+
     def _mult(self, rate_mult, rate_mult_row, N):
         """rate_mult_table for this mechanism's nrg + nrs reactions; (None, None) without multipliers"""
         if rate_mult is None and rate_mult_row is None:
@@ -306,8 +340,10 @@ class Engine:
         knot arrays). T is then not read (None is fine), u0 is the caller's state at T(0), and the run
         uses the wavefront engine.
         energy="adiabatic": adiabatic constant-volume reactors (br_opts.energy): T is T(0) and becomes a state
-        component, the stats carry "T_end" [N] and, with tout, "T_out" [N, nout]; gas-only mechanisms, the
-        wavefront engine with CVODE's DQ Jacobian (dq_jacobian is not read), not together with tprog."""
+        component, the stats carry "T_end" [N] and, with tout, "T_out" [N, nout]; gas-only mechanisms, CVODE's DQ
+        Jacobian (dq_jacobian is not read), not together with tprog. The wavefront engine runs it, or, with env
+        BRHIP_ENGINE = quad (ng + 1 <= 16) / pair (ng + 1 <= 32), the group engine's energy instance
+        (energy_launch_info, energy_kernel_name)."""
         u = np.array(np.atleast_2d(u0), dtype=np.float64, order="C")
         N = u.shape[0]
         mult, mrow = self._mult(rate_mult, rate_mult_row, N)

@@ -120,8 +120,13 @@ typedef struct br_opts {
                                  cannot produce a NaN from log. The NaN-state check covers the T component;
                                  the opt-in unstable_factor test looks at the species only. Error weight of
                                  T: 1 / (rtol |T| + atol), as for any other component. Gas-only mechanisms
-                                 with ng + 1 <= 56 (else BR_ERR_UNSUPPORTED). An energy run always uses the
-                                 wavefront engine and CVODE's DQ Jacobian over ng + 1 columns: dq_jacobian
+                                 with ng + 1 <= 56 (else BR_ERR_UNSUPPORTED). An energy run uses the
+                                 wavefront engine, unless env BRHIP_ENGINE asks for the group engine of its
+                                 width -- quad with ng + 1 <= 16, pair with 16 < ng + 1 <= 32 -- and the
+                                 mechanism has a group energy instance (<= 32 third-body efficiency sets,
+                                 the instance fits the LDS): then k_group<GL, NM, true> runs it, four or two
+                                 reactors per wave (br_mech_energy_launch_info tells which). Either engine
+                                 builds CVODE's DQ Jacobian over ng + 1 columns: dq_jacobian
                                  is not read, nfe_dq == nje * (ng + 1). Rate multipliers, tout,
                                  tout_per_reactor, the ignition marker, hmax and max_steps behave as in an
                                  isothermal run. Not together with ntprog (BR_ERR_INPUT), any other value
@@ -281,6 +286,14 @@ int br_mech_engine(const br_mech* m);
  * reactors per workgroup, resident waves per CU (occupancy calculator: VGPRs and LDS), LDS bytes
  * per workgroup (staged tables + one block per reactor or group). Any pointer may be NULL. */
 int br_mech_launch_info(const br_mech* m, int* rpb, int* waves_per_cu, long long* lds_bytes);
+/* the same for an energy run (br_opts.energy) of this handle under the current BRHIP_ENGINE: *engine = 0 (the
+ * wavefront energy instance) or -(100 GL + NM) (the group energy instance k_group<GL, NM, true>, (GL, NM) from
+ * ng + 1: <= 9: (16, 9), <= 16: (16, 16), <= 24: (32, 24), <= 32: (32, 32)), its reactors per workgroup,
+ * resident waves per CU and LDS bytes per workgroup, and *resident, the reactors in flight at once on its
+ * persistent grid. The shapes are found at the first call (or energy run) and kept in the handle. Any out pointer
+ * may be NULL. A null handle is BR_ERR_INPUT; a surface mechanism or ng + 1 > 56 BR_ERR_UNSUPPORTED, as an
+ * energy run. */
+int br_mech_energy_launch_info(br_mech* m, int* engine, int* rpb, int* waves_per_cu, long long* lds_bytes, int* resident);
 
 /* host-buffer entry points (copy in/out); arrays are reactor-major */
 int br_rates(br_mech* m, int N, const double* T, const double* p, const double* x /*[N][ng]*/,
@@ -419,6 +432,16 @@ int br_debug_wave_eval(br_mech* m, int N, const double* T, const double* Asv, co
  * Multipliers as br_debug_lane_eval. BR_ERR_UNSUPPORTED as an energy run. */
 int br_debug_energy_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
                          const int* rate_mult_row, double* du /*[N][ng+1]*/);
+
+/* group energy check (tests): the same right-hand side as the energy instance of the group engine evaluates it
+ * (k_group<GL, NM, true>, (GL, NM) from ng + 1), through its own device functions, workgroup shape, LDS blocks and
+ * global slots. At most two workgroups: each group evaluates its reactors one after another in the same block and
+ * slot; the constants and the lanes' e_k, cv_k are first built at another temperature, then rebuilt at T in the
+ * live slot (the refresh path). Multipliers as br_debug_lane_eval. BR_ERR_UNSUPPORTED when the mechanism has no
+ * group energy instance: ng + 1 > 32, surface species, or more than 32 efficiency sets. Does not read
+ * BRHIP_ENGINE. */
+int br_debug_group_energy_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
+                               const int* rate_mult_row, double* du /*[N][ng+1]*/);
 
 /* temperature-programme check (tests): Tout[i][k] = T(t[i][k]) of reactor i's programme, through the
  * device evaluator the integrator calls (one thread per reactor; consecutive times of a row reuse the

@@ -134,6 +134,25 @@ function mech_create(desc::Ref{BrMechDesc}, device::Integer=0)
 end
 mech_destroy(m::Ptr{Cvoid}) = check(ccall((:br_mech_destroy, lib), Cint, (Ptr{Cvoid},), m))
 
+"""Launch geometry of the engine `integrate!` uses for this mechanism (br_mech_launch_info)."""
+function launch_info(m::Ptr{Cvoid})
+    rpb = Ref{Cint}(0); wpc = Ref{Cint}(0); lds = Ref{Clonglong}(0)
+    check(ccall((:br_mech_launch_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Clonglong}), m, rpb, wpc, lds))
+    return (reactors_per_workgroup=Int(rpb[]), waves_per_cu=Int(wpc[]), lds_bytes_per_workgroup=Int(lds[]))
+end
+
+"""Engine and launch geometry of an energy run (`with_energy`) of this mechanism under the current BRHIP_ENGINE
+(br_mech_energy_launch_info): `engine` 0 = the wavefront energy instance, -(100 GL + NM) = the group energy instance
+k_group<GL, NM, true> (BRHIP_ENGINE = quad with ng + 1 <= 16, pair with ng + 1 <= 32); `resident` = reactors in
+flight at once on its persistent grid."""
+function energy_launch_info(m::Ptr{Cvoid})
+    e = Ref{Cint}(0); rpb = Ref{Cint}(0); wpc = Ref{Cint}(0); lds = Ref{Clonglong}(0); res = Ref{Cint}(0)
+    check(ccall((:br_mech_energy_launch_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ref{Clonglong}, Ref{Cint}),
+                m, e, rpb, wpc, lds, res))
+    return (engine=Int(e[]), reactors_per_workgroup=Int(rpb[]), waves_per_cu=Int(wpc[]),
+            lds_bytes_per_workgroup=Int(lds[]), resident=Int(res[]))
+end
+
 """N reactors 0 -> tf (br_integrate). `u` is n x N column-major in Julia, i.e. the reactor-major
 [N][n] rows of the C layout; it is overwritten with the end states. Returns the NSTAT x N stats."""
 function integrate!(m::Ptr{Cvoid}, T::Vector{Float64}, Asv::Vector{Float64}, u::Matrix{Float64},
