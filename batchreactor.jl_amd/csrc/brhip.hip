@@ -76,6 +76,11 @@ __host__ __device__ constexpr int br_wpe(int nmax) {
 // KOptsEnergy, carry T as component ng (lane ng) of a system of nsys = ng + 1 equations, refresh the constants
 // before any RHS whose T differs from the cached one, and always build CVODE's DQ Jacobian; everything under
 // `if constexpr (ENERGY)` is theirs alone.
+// The instances that keep a lane's first two {kf, kr} pairs and its molar mass in registers between setups
+// (KReg): n in 33..56, isothermal or with a programme (a programme's refresh reloads them). Not the energy
+// instance, which refreshes the constants twice per DQ Jacobian, and not NMAX = 64: with two pairs held (the form
+// with the first pass unrolled) their scratch grew, 120 -> 160 B and 68 -> 84 B. NMAX = 16 / 32 / 72 spill already.
+__host__ __device__ constexpr bool kreg_on(int nmax, bool energy) { return nmax == 56 && !energy; }
 template <int NMAX, bool TPROG = false, bool ENERGY = false>
 __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_per_eu(br_wpe(NMAX), 8))) void k_integrate(
     DevMech M, int N, int rpb, const double* __restrict__ Tv, const double* __restrict__ Asvv, double* __restrict__ U,
@@ -83,6 +88,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     br_stats* __restrict__ stats, double* __restrict__ Jws, double* __restrict__ trace) {
     static_assert(!(TPROG && ENERGY) && (!ENERGY || NMAX <= 56), "energy instances: no programme, one component per lane");
     constexpr int CPL = NMAX > 64 ? 2 : 1;   // components per lane
+    constexpr bool KR = kreg_on(NMAX, ENERGY);
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const WaveCtx W = [&] {
         if constexpr (ENERGY) return energy_wave_ctx<NMAX>(M, smem_raw, rpb, Jws);
@@ -139,6 +145,8 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
     C->a_ign = o.ign; C->a_nout = o.nout; C->a_tout = o.tout; C->a_yout = o.yout;
 
     init_tconst<CPL, true>(M, tb, S, T, lane, rid);
+    KReg<KR> kq;   // the lane's first two {kf, kr} pairs and its molar mass (brhip_device.hpp, KReg: lifetime)
+    kreg_load(kq, tb, S, lane);
     if constexpr (ENERGY) energy_thermo(lane, n, T, ek, cvk);
 
     // ---- CVodeInit
@@ -228,6 +236,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
                 T = Tt;
                 wave_sync();
                 init_tconst<CPL, true>(M, tb, S, T, lane, rid);
+                kreg_load(kq, tb, S, lane);
             }
         }
     };
@@ -260,7 +269,7 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
             BR_CLK(c0);
             tprog_refresh();
             energy_refresh(y[0]);
-            rhs<CPL>(M, tb, S, T, Asv, Asv_th, y, lane, p_last, f);
+            rhs<CPL, KR>(M, tb, S, T, Asv, Asv_th, y, lane, p_last, f, kq);
             if constexpr (ENERGY) {   // f[ng] = dT/dt from the du just computed (lane ng's f was 0)
                 const double Td = energy_tdot(tb, lane, n, y[0], f[0], ek, cvk);
                 if (lane == n) f[0] = Td;
@@ -309,6 +318,9 @@ __global__ __launch_bounds__(64 * br_maxrpb(NMAX)) __attribute__((amdgpu_waves_p
             BR_CLK(c1);
             if constexpr (CPL == 1) lu_fail = lu_factor<NMAX>(Jsave, LUsave, ud(C->gamma), nsys, lane, perm[0]);
             else lu_fail = lu_factor2<NMAX>(Jsave, LUsave, scr, ud(C->gamma), nsys, lane, perm);
+            // the registers were dead across the setup: the pairs again from the slot (lu_solve's entry
+            // drains the memory counter, so their latency runs under it)
+            kreg_load(kq, tb, S, lane);
             BR_ACC(cyc_lu, c1);
         }
         double delta[CPL];

@@ -11,7 +11,8 @@
 //  * per reactor block: [Ctl][V: Nordsieck + work vectors][SP: conc | accw | accs (64 each)]
 //      [FOD: {k0/k_inf, log10 Fcent, c, n} per falloff reaction][SKD: {k, k*exp(cov)} per surface reaction]
 //  * RXD: {kf, kr} per gas reaction, in the wave's global workspace slot (5.2 KB for GRI: kept
-//    out of LDS so 12 reactors fit a CU instead of 8), prefetched at the start of each RHS
+//    out of LDS so 12 reactors fit a CU instead of 8), prefetched at the start of each RHS; k_integrate<56>
+//    keeps a lane's first two pairs in registers between setups instead (KReg)
 //  * T-dependent rate constants (RXD/FOD/SKD) are computed once per reactor: T is a per-reactor
 //    constant (ConstantParams, src/BatchReactor.jl:14-17).
 // Reactions are evaluated lane-parallel (reaction r on lane r mod 64); production rates are
@@ -393,6 +394,30 @@ __device__ __forceinline__ KPre rx_prefetch(const RView& R, int lane) {
     k.b = kpair(R.rxd, lane + WAVE < nrg ? lane + WAVE : 0);
     return k;
 }
+// The third home of {kf, kr}, after init_tconst's stores and the wave's global slot: reaction r is always
+// evaluated by lane r mod 64, so the pairs of r = lane and r = lane + 64 -- what rx_prefetch loads at every RHS
+// -- can stay in the lane's registers, with its molar mass (8 + 2 VGPRs). KReg<true>, the isothermal and
+// programme instances of k_integrate for n in 33..56 (GRI: kreg_on); KReg<false> is empty and the RHS loads as
+// before (the parity kernels, the other instances). Lifetime: kreg_load after every init_tconst (a wave's
+// next reactor, a programme's T refresh) and after every lu_factor, so the registers are dead across
+// jacobian() and lu_factor(), the phases at the kernel's VGPR peak, and valid at every rhs() in between, those
+// of a DQ column loop included. The reactions past the first two pairs keep the loop's own loads: six pairs (all
+// of GRI's), with the loop unrolled over them, measured the same +2.0 % but spill one dword more than the
+// parent build, and the unrolled two-pair form gained 0.8 %.
+template <bool ON>
+struct KReg {
+    KPre k;
+    double mw;   // molwt[lane]: constant for the mechanism, one LDS read per load instead of one per RHS
+};
+template <>
+struct KReg<false> {};
+template <bool ON>
+__device__ __forceinline__ void kreg_load(KReg<ON>& K, const Tab& tb, const RView& R, int lane) {
+    if constexpr (ON) {
+        K.k = rx_prefetch(R, lane);
+        K.mw = tb.molwt[lane];
+    }
+}
 template <int CPL>
 __device__ __forceinline__ void production(const DevMech& M, const Tab& tb_, const RView& R_, double RT, int lane,
                                            KPre kp) {
@@ -441,15 +466,19 @@ __device__ __forceinline__ void production(const DevMech& M, const Tab& tb_, con
 
 // residual! (src/BatchReactor.jl:312-376) for the components of `lane` (lane + 64 s, s < CPL):
 // du[s]; writes the diagnosed pressure to *p_out (save_data semantics).
-template <int CPL>
+// kq: the lane's register-held pairs and molar mass (KReg; KR = false: loaded here)
+template <int CPL, bool KR = false>
 __device__ __forceinline__ void rhs(const DevMech& M, const Tab& tb_, const RView& R_, double T, double Asv,
                                     double Asv_th, const double (&u)[CPL], int lane, double* p_out,
-                                    double (&du)[CPL]) {
+                                    double (&du)[CPL], const KReg<KR>& kq = KReg<KR>{}) {
+    static_assert(!KR || CPL == 1, "KReg: one component per lane");
     typedef Lay<CPL> L;
     const Tab tb = tab_view<CPL>(br_lds, M);
     const RView R = R_;
     BR_SUB_T(rt0);
-    const KPre kp = rx_prefetch(R, lane);
+    KPre kp;
+    if constexpr (KR) kp = kq.k;
+    else kp = rx_prefetch(R, lane);
     const int ng = MF(ng), n = MF(n);
     // Y = u/rho, x = (Y/M)/sum(Y/M), p = rho R T / Mbar (:326-338 / :349-353) give the gas
     // concentrations c_k = p x_k / (R T) = u_k / M_k exactly; p = R T sum_k c_k
@@ -458,7 +487,8 @@ __device__ __forceinline__ void rhs(const DevMech& M, const Tab& tb_, const RVie
     for (int s = 0; s < CPL; ++s) {
         const int k = lane + 64 * s;
         const bool gas = k < ng;
-        Mk[s] = tb.molwt[k];
+        if constexpr (KR) Mk[s] = kq.mw;
+        else Mk[s] = tb.molwt[k];
         const double c = gas ? u[s] / Mk[s] : u[s];
         if (k < n) { R.sp[L::CONC + k] = c; R.sp[L::ACCW + k] = 0.0; R.sp[L::ACCS + k] = 0.0; }
         cg += gas ? c : 0.0;
@@ -1217,7 +1247,8 @@ __device__ __forceinline__ double lu_solve(const double* __restrict__ ws, int n,
     // one buffer descriptor over factors + D^-1: every load of the solve is a buffer load, so the
     // waitcnt pass can count them in order (a global load among them forces vmcnt(0)); nothing
     // issued before the solve may still be pending either (a flat or scratch access of the
-    // controller would make the counter out of order too), so drain it first
+    // controller would make the counter out of order too; after a setup, kreg_load's two global
+    // loads, whose latency this wait covers), so drain it first
     __builtin_amdgcn_s_waitcnt(0x70);   // vmcnt(0) lgkmcnt(0)
     const __amdgpu_buffer_rsrc_t rs =
         __builtin_amdgcn_make_buffer_rsrc((void*)wsg, (short)0, (NMAX * NMAX + WAVE) * 8, 0x00020000);
