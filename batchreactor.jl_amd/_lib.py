@@ -56,7 +56,7 @@ EXPORTS = ["br_version", "br_last_error", "br_device_count", "br_mech_create", "
            "br_integrate_host", "br_phase_tout_dev", "br_integrate_phase", "br_debug_group_eval",
            "br_debug_group_lu_solve", "br_sensitivity", "br_debug_tprog_eval", "br_debug_lane_eval",
            "br_debug_lane_lu_solve", "br_debug_wave_eval", "br_debug_energy_eval", "br_mech_energy_launch_info",
-           "br_debug_group_energy_eval"]
+           "br_debug_group_energy_eval", "br_debug_wave_lu"]
 
 # br_integrate_host callbacks: int f(void* user, double t, const double* u, double* du);
 # void cb(void* user, double t, const double* u)
@@ -115,6 +115,8 @@ def lib():
     L.br_mech_energy_launch_info.restype = C.c_int
     L.br_debug_group_energy_eval.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, ip, dp]
     L.br_debug_group_energy_eval.restype = C.c_int
+    L.br_debug_wave_lu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, ip, dp, ip, ip, dp]
+    L.br_debug_wave_lu.restype = C.c_int
     cs = C.c_char_p
     L.br_mech_parse.argtypes = [cs, cs, cs, cs, C.c_int, C.POINTER(vp)]
     L.br_host_mech_desc.argtypes = [vp, C.POINTER(MechDesc)]

@@ -613,7 +613,7 @@ struct Stage {
 
 extern "C" {
 
-int br_version(void) { return 231; }   // 231: br_mech_energy_launch_info, br_debug_group_energy_eval (br_opts as in 230)
+int br_version(void) { return 232; }   // 232: br_debug_wave_lu; 231: br_mech_energy_launch_info, br_debug_group_energy_eval (br_opts as in 230)
 const char* br_last_error(void) { return g_err.c_str(); }
 int br_device_count(void) {
     int c = 0;

@@ -111,6 +111,149 @@ extern "C" int br_debug_lu_solve(int N, int n, const double* J, const double* ga
 }
 
 // ------------------------------------------------------------------------------------
+// wavefront LU check (tests): lu_factor + lu_solve (lu_factor2 + lu_solve2) the way k_integrate strings them
+// together: every factorization is solved with at once, the next one loads its rows in the pivot order the
+// last one left, the factor area may hold anything before a factorization (in the integrator: the Jacobian
+// scratch), wpb waves share a workgroup, each on its own LDS scratch and workspace slot, and a slot is
+// reused by the wave's next matrix.
+// ------------------------------------------------------------------------------------
+namespace {
+struct WaveLuArgs {
+    int N, n, wpb, dirty;
+    const double *J0, *J1, *g0, *g1, *b;
+    const int* perm_in;
+    double* x;      // [2][N][n]
+    int* fail;      // [2][N]
+    int* perm;      // [2][N][n]
+    double* F;      // [2][N][lu_ws_doubles(NMAX)]
+    double* ws;     // [slots][NMAX * col_rows(NMAX) + lu_ws_doubles(NMAX)]
+};
+// matrices slot, slot + G, ... (G = waves of the grid) one after another in the wave's slot. Leg A: I - g0 J0
+// with the rows placed as perm_in says (identity when null); leg B: I - g1 J1 (null: leg A's) with the rows in
+// leg A's pivot order. One copy of the factorization and of the solve (the leg loop stays rolled).
+template <int NMAX>
+__global__ __launch_bounds__(64 * br_maxrpb(NMAX)) void k_wave_lu(WaveLuArgs a) {
+    constexpr int CPL = NMAX > 64 ? 2 : 1;
+    constexpr int JW = NMAX > 64 ? CR2 : 64;                            // column stride of the saved J (col_rows)
+    constexpr int FD = NMAX > 64 ? (NMAX + 1) * CR2 : NMAX * NMAX + WAVE;   // lu_ws_doubles(NMAX)
+    constexpr int SCR = Lay<CPL>::DOUBLES - Lay<CPL>::ACCW;             // k_integrate's scr: the species block from ACCW on
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int wave = uni((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int slot = (int)blockIdx.x * a.wpb + wave;
+    const int G = (int)gridDim.x * a.wpb;
+    const int N = a.N, n = a.n;
+    LDSd* scr = (LDSd*)(reinterpret_cast<double*>(smem_raw) + wave * SCR);
+    double* Jsave = a.ws + (size_t)slot * (NMAX * JW + FD);
+    double* LUsave = Jsave + NMAX * JW;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const double pad = a.dirty ? qnan : 0.0;
+    for (int rid = slot; rid < N; rid += G) {
+        wave_sync();
+        int perm[CPL];
+#pragma unroll
+        FOR_S perm[s] = (a.perm_in && CS < n) ? a.perm_in[(size_t)rid * n + CS] : CS;
+        if (a.dirty)
+            for (int i = lane; i < FD; i += 64) LUsave[i] = qnan;
+#pragma unroll 1
+        for (int leg = 0; leg < 2; ++leg) {
+            const double* J = (leg && a.J1) ? a.J1 : a.J0;
+            const double gam = uni((leg && a.g1) ? a.g1[rid] : a.g0[rid]);
+            // the saved J as jacobian() leaves it: column-major, JW rows per column, row per lane
+#pragma unroll 1
+            for (int j = 0; j < NMAX; ++j)
+#pragma unroll
+                FOR_S if (CS < JW) Jsave[j * JW + CS] = (CS < n && j < n) ? J[((size_t)rid * n + CS) * n + j] : pad;
+            wave_sync();
+            int f;
+            if constexpr (CPL == 1) f = lu_factor<NMAX>(Jsave, LUsave, gam, n, lane, perm[0]);
+            else f = lu_factor2<NMAX>(Jsave, LUsave, scr, gam, n, lane, perm);
+            wave_sync();
+            const size_t o = (size_t)leg * N + rid;
+            if (!f) {                                                   // (k_integrate: no solve after a zero pivot)
+                double r[CPL];
+#pragma unroll
+                FOR_S r[s] = CS < n ? a.b[(size_t)rid * n + CS] : 0.0;
+                if constexpr (CPL == 1) r[0] = lu_solve<NMAX>(LUsave, n, lane, perm[0], r[0], scr);
+                else lu_solve2<NMAX>(LUsave, scr, n, lane, perm, r);
+#pragma unroll
+                FOR_S if (CS < n) a.x[o * n + CS] = r[s];
+            }
+#pragma unroll
+            FOR_S if (CS < n) a.perm[o * n + CS] = perm[s];
+            if (lane == 0) a.fail[o] = f;
+            for (int i = lane; i < FD; i += 64) a.F[o * FD + i] = LUsave[i];
+            wave_sync();
+        }
+    }
+}
+}  // namespace
+
+extern "C" int br_debug_wave_lu(int N, int n, int wpb, int dirty, const double* J0, const double* J1, const double* gamma0,
+                                const double* gamma1, const double* b, const int* perm_in, double* x, int* fail_out,
+                                int* perm, double* F) {
+    if (N <= 0 || n < 1 || n > 72 || !J0 || !gamma0 || !b || !x || !fail_out || !perm || !F) return fail_code_input();
+    const int nmax = nmax_of(n);
+    if (wpb < 1 || wpb > br_maxrpb(nmax)) return fail(BR_ERR_INPUT, "wpb: 1 .. br_maxrpb(nmax) waves per workgroup");
+    if (perm_in) {
+        std::vector<char> seen(n);
+        for (int i = 0; i < N; ++i) {
+            std::fill(seen.begin(), seen.end(), 0);
+            for (int s = 0; s < n; ++s) {
+                const int r = perm_in[(size_t)i * n + s];
+                if (r < 0 || r >= n || seen[r]) return fail(BR_ERR_INPUT, "perm_in: not a permutation of 0..n-1");
+                seen[r] = 1;
+            }
+        }
+    }
+    // small fixed grid: one workgroup up to 4 wpb matrices, else two (as br_debug_wave_eval), so that every
+    // wave takes further matrices in the slot of its first from N = 2 wpb (one workgroup) or 4 wpb (two) on
+    const int blocks = std::min(2, (N + 4 * wpb - 1) / (4 * wpb));
+    const size_t fd = lu_ws_doubles(nmax), slot = (size_t)nmax * col_rows(nmax) + fd, nn = (size_t)N * n;
+    const size_t scr = nmax > 64 ? Lay<2>::DOUBLES - Lay<2>::ACCW : Lay<1>::DOUBLES - Lay<1>::ACCW;
+    double *dJ0, *dJ1 = nullptr, *dg0, *dg1 = nullptr, *db, *dx, *dF, *dws;
+    int *dpi = nullptr, *df, *dp;
+    DevScratch S;
+    HIPCHK(S.alloc(&dJ0, nn * n * 8));
+    HIPCHK(S.alloc(&dg0, (size_t)N * 8));
+    HIPCHK(S.alloc(&db, nn * 8));
+    HIPCHK(S.alloc(&dx, 2 * nn * 8));
+    HIPCHK(S.alloc(&df, 2 * (size_t)N * 4));
+    HIPCHK(S.alloc(&dp, 2 * nn * 4));
+    HIPCHK(S.alloc(&dF, 2 * (size_t)N * fd * 8));
+    HIPCHK(S.alloc(&dws, (size_t)blocks * wpb * slot * 8));
+    HIPCHK(hipMemcpy(dJ0, J0, nn * n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dg0, gamma0, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, b, nn * 8, hipMemcpyHostToDevice));
+    if (J1) {
+        HIPCHK(S.alloc(&dJ1, nn * n * 8));
+        HIPCHK(hipMemcpy(dJ1, J1, nn * n * 8, hipMemcpyHostToDevice));
+    }
+    if (gamma1) {
+        HIPCHK(S.alloc(&dg1, (size_t)N * 8));
+        HIPCHK(hipMemcpy(dg1, gamma1, (size_t)N * 8, hipMemcpyHostToDevice));
+    }
+    if (perm_in) {
+        HIPCHK(S.alloc(&dpi, nn * 4));
+        HIPCHK(hipMemcpy(dpi, perm_in, nn * 4, hipMemcpyHostToDevice));
+    }
+    // (x starts from the caller's values: a matrix with a zero pivot writes none)
+    HIPCHK(hipMemcpy(dx, x, 2 * nn * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dws, 0, (size_t)blocks * wpb * slot * 8));
+    const WaveLuArgs a{N, n, wpb, dirty != 0, dJ0, dJ1, dg0, dg1, db, dpi, dx, df, dp, dF, dws};
+    const void* fn = nmax == 16 ? (const void*)k_wave_lu<16> : nmax == 32 ? (const void*)k_wave_lu<32>
+                   : nmax == 56 ? (const void*)k_wave_lu<56> : nmax == 64 ? (const void*)k_wave_lu<64>
+                                                                            : (const void*)k_wave_lu<72>;
+    void* args[] = {(void*)&a};
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * wpb), args, (size_t)wpb * scr * 8, 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(x, dx, 2 * nn * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(fail_out, df, 2 * (size_t)N * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(perm, dp, 2 * nn * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(F, dF, 2 * (size_t)N * fd * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------
 // group-engine checks (tests): the device functions of k_group (brhip_group.hpp) on their own, with
 // k_group's workgroup shape, LDS blocks, global slots and buffer-resource Jacobian stores
 // ------------------------------------------------------------------------------------

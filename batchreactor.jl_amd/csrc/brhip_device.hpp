@@ -845,8 +845,10 @@ __device__ __forceinline__ void jacobian(const DevMech& M, const Tab& tb_, const
 // physical row swaps during the factorization (see LUWs for the stored form).
 // Pivot search on the bit patterns of |a_ik| (monotone for non-negative doubles): a 32-bit
 // DPP max over the high words, a second pass over the low words only when the high words tie,
-// then, among candidates holding the max, the one with the lowest ORIGINAL row index = the first
-// max in row order (the rows sit in lanes in the previous factorization's pivot order, lu_factor).
+// then, among candidates holding the max, the one denseGETRF finds first: the lowest position in
+// denseGETRF's interchanged row order (getrf_pos; the original row index until an interchange has
+// moved the row). The rows sit in lanes in the previous factorization's pivot order (lu_factor); the
+// choice does not depend on that placement.
 // ------------------------------------------------------------------------------------
 // Wave max of a 32-bit value: 4 DPP steps inside each 16-lane row, then row_bcast:15 carries row r's
 // max into row r + 1 (rows 1, 3) and row_bcast:31 row 1's into rows 2 and 3, so lane 63 holds the
@@ -873,10 +875,24 @@ __device__ __forceinline__ unsigned wave_umax(unsigned x) {
         : "v"(x));
     return __builtin_amdgcn_readlane(r, 63);
 }
+// Position of this lane's row in denseGETRF's row order before step k: denseGETRF exchanges the pivot
+// row with the row at position j at every step j, so a row that was passed over sits where the pivot
+// of that step came from. Steps 0..k-1 replayed from the lanes' pstep (the step a lane's row was the
+// pivot of; none for a candidate), starting from the original row index. Only an exact tie asks.
+__device__ __forceinline__ int getrf_pos(int prow, int pstep, int k) {
+    int d = prow;
+#pragma unroll 1
+    for (int j = 0; j < k; ++j) {
+        const int pl = (int)__builtin_ctzll(__ballot(pstep == j));   // lane of step j's pivot row
+        const int P = __builtin_amdgcn_readlane(d, pl);              // where that row was
+        d = (pstep == j) ? j : (d == j ? P : d);
+    }
+    return d;
+}
 // a = a_ik, cm = 0x7fffffff on candidate rows (not pivoted yet), 0 elsewhere; prow = original row
-// index held by this lane. hi = high word of |a_ik| on candidates, 0 elsewhere, so when the max is
-// not 0 the lanes holding it are candidates (one compare for the ballot).
-__device__ __forceinline__ int pivot_lane(double a, unsigned cm, int prow) {
+// index held by this lane, pstep its pivot step, k the step. hi = high word of |a_ik| on candidates,
+// 0 elsewhere, so when the max is not 0 the lanes holding it are candidates (one compare for the ballot).
+__device__ __forceinline__ int pivot_lane(double a, unsigned cm, int prow, int pstep, int k) {
     const unsigned long long bits = (unsigned long long)__double_as_longlong(a);
     const unsigned hi = (unsigned)(bits >> 32) & cm;
     const unsigned mh = wave_umax(hi);
@@ -887,8 +903,9 @@ __device__ __forceinline__ int pivot_lane(double a, unsigned cm, int prow) {
         const unsigned ml = wave_umax(lo);
         const bool top2 = top && lo == ml;
         m = __ballot(top2);
-        if (__builtin_popcountll(m) > 1) {   // an exact tie: the first in original row order
-            const unsigned key = top2 ? ~(unsigned)prow : 0u;
+        if (__builtin_popcountll(m) > 1) {   // an exact tie: the first in denseGETRF's row order
+            const int pos = getrf_pos(prow, pstep, k);   // (every lane: it votes and is read across the wave)
+            const unsigned key = top2 ? ~(unsigned)pos : 0u;
             const unsigned mk = wave_umax(key);
             m = __ballot(top2 && key == mk);
         }
@@ -946,7 +963,7 @@ __device__ __forceinline__ void lu_rl_steps(double (&a)[W], int k0, int k1, int 
         const double akk = bcast(a[0], k);
         const bool kcand = (__ballot(cand) >> k) & 1ull;
         const bool fast = kcand && __ballot(cand && lane != k && !(fabs(a[0]) < fabs(akk))) == 0;
-        const int p = fast ? k : pivot_lane(a[0], cand ? 0x7fffffffu : 0u, prow);
+        const int p = fast ? k : pivot_lane(a[0], cand ? 0x7fffffffu : 0u, prow, pstep, k);
         const double piv = fast ? akk : bcast(a[0], p);
         if (piv == 0.0 && !fail) fail = k + 1;
         const double rinv = 1.0 / piv;
@@ -996,7 +1013,7 @@ __device__ __forceinline__ double lane_pull(double v, int src) {
 // the gather pass (a read and a write of the whole matrix, ~9 MB per GRI reactor) is skipped.
 // Otherwise the rows of M are gathered into step order (in place) as before. D^-1 is stored in
 // step order. Row placement does not change the arithmetic: each row gets the same FMAs, and ties
-// in the pivot search go to the lowest original row. Returns 0 or k+1 for a zero pivot; perm_io:
+// in the pivot search go to the row denseGETRF takes. Returns 0 or k+1 for a zero pivot; perm_io:
 // step s -> original row on return.
 template <int NMAX>
 __device__ __forceinline__ int lu_factor(const double* __restrict__ J_, double* __restrict__ ws, double gamma, int n,
@@ -1274,8 +1291,22 @@ __device__ __forceinline__ double lu_solve(const double* __restrict__ ws, int n,
 // ------------------------------------------------------------------------------------
 constexpr int CR2 = 80;
 
-// first max |a| over candidate positions; exact ties go to the lowest ORIGINAL row (prow)
-__device__ __forceinline__ int pivot_row2(double v0, bool c0, double v1, bool c1, const int (&prow)[2]) {
+// getrf_pos for two positions per lane
+__device__ __forceinline__ void getrf_pos2(const int (&prow)[2], const int (&pstep)[2], int k, int (&d)[2]) {
+    d[0] = prow[0];
+    d[1] = prow[1];
+#pragma unroll 1
+    for (int j = 0; j < k; ++j) {
+        const unsigned long long b0 = __ballot(pstep[0] == j), b1 = __ballot(pstep[1] == j);
+        const int P = b0 ? __builtin_amdgcn_readlane(d[0], (int)__builtin_ctzll(b0))
+                         : __builtin_amdgcn_readlane(d[1], (int)__builtin_ctzll(b1));
+        d[0] = (pstep[0] == j) ? j : (d[0] == j ? P : d[0]);
+        d[1] = (pstep[1] == j) ? j : (d[1] == j ? P : d[1]);
+    }
+}
+// first max |a| over candidate positions; exact ties go to the first in denseGETRF's row order
+__device__ __forceinline__ int pivot_row2(double v0, bool c0, double v1, bool c1, const int (&prow)[2],
+                                          const int (&pstep)[2], int k) {
     const unsigned long long b0 = (unsigned long long)__double_as_longlong(v0);
     const unsigned long long b1 = (unsigned long long)__double_as_longlong(v1);
     const unsigned h0 = c0 ? (unsigned)(b0 >> 32) : 0u, h1 = c1 ? (unsigned)(b1 >> 32) : 0u;
@@ -1289,8 +1320,10 @@ __device__ __forceinline__ int pivot_row2(double v0, bool c0, double v1, bool c1
         t1 = t1 && l1 == ml;
         m0 = __ballot(t0);
         m1 = __ballot(t1);
-        if (__builtin_popcountll(m0) + __builtin_popcountll(m1) > 1) {   // exact tie: lowest original row
-            const unsigned k0 = t0 ? ~(unsigned)prow[0] : 0u, k1 = t1 ? ~(unsigned)prow[1] : 0u;
+        if (__builtin_popcountll(m0) + __builtin_popcountll(m1) > 1) {   // exact tie
+            int d[2];
+            getrf_pos2(prow, pstep, k, d);
+            const unsigned k0 = t0 ? ~(unsigned)d[0] : 0u, k1 = t1 ? ~(unsigned)d[1] : 0u;
             const unsigned mk = wave_umax(max(k0, k1));
             m0 = __ballot(t0 && k0 == mk);
             m1 = __ballot(t1 && k1 == mk);
@@ -1310,7 +1343,7 @@ __device__ __forceinline__ void lu_rl_steps2(double (&a)[2][W], int k0, int k1, 
     const unsigned fo8[2] = {(unsigned)lane * 8u, (unsigned)min(64 + lane, CR2 - 1) * 8u};
 #pragma unroll 1
     for (int k = k0; k < k1; ++k) {
-        const int pr = pivot_row2(fabs(a[0][0]), pstep[0] < 0, fabs(a[1][0]), pstep[1] < 0, prow);
+        const int pr = pivot_row2(fabs(a[0][0]), pstep[0] < 0, fabs(a[1][0]), pstep[1] < 0, prow, pstep, k);
         const int p = pr & 63, ps = pr >> 6;
         const double piv = ps ? bcast(a[1][0], p) : bcast(a[0][0], p);
         if (piv == 0.0 && !fail) fail = k + 1;

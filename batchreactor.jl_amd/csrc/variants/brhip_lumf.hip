@@ -57,7 +57,7 @@ __device__ __forceinline__ void lu_mf_panel(double (&a)[PW], double (&e)[PW], in
         if (kk < nlive) {
             const int k = c0 + kk;
             const bool cand = pstep < 0;
-            const int p = pivot_lane(a[kk], cand ? 0x7fffffffu : 0u, prow);
+            const int p = pivot_lane(a[kk], cand ? 0x7fffffffu : 0u, prow, pstep, k);
             piv[kk] = p;
             const double pv = bcast(a[kk], p);
             if (pv == 0.0 && !fail) fail = k + 1;

@@ -255,6 +255,29 @@ class Engine:
                                                      _lib.dptr(x), _lib.iptr(f), _lib.iptr(piv)))
         return x, f, piv
 
+    @staticmethod
+    def wave_lu(J0, gamma0, b, J1=None, gamma1=None, perm_in=None, wpb=1, dirty=True, fill=-7.0):
+        """(x, fail, perm, F) of the wavefront integrator's LU and solve (br_debug_wave_lu: lu_factor / lu_solve, for
+        n > 64 lu_factor2 / lu_solve2, in k_integrate's order of calls). Leg A factors I - gamma0 J0 with the rows
+        placed as perm_in [N, n] says (None: the identity) and solves b; leg B factors I - gamma1 J1 (None: leg A's
+        matrix) in leg A's pivot order and solves b. x [2, N, n] (entries of a matrix with a zero pivot keep `fill`),
+        fail [2, N], perm [2, N, n] (the original row of each step), F [2, N, W] the factor workspace in the device
+        layout (include/brhip.h). wpb: waves per workgroup; dirty: NaNs in the workspace before leg A."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        N, n = b.shape
+        c = lambda a, t=np.float64: None if a is None else np.ascontiguousarray(a, dtype=t)
+        J0, J1, g0, g1, pin = c(J0), c(J1), c(gamma0), c(gamma1), c(perm_in, np.int32)
+        nmax = 16 if n <= 16 else 32 if n <= 32 else 56 if n <= 56 else 64 if n <= 64 else 72
+        W = (nmax + 1) * 80 if nmax > 64 else nmax * nmax + 64
+        x = np.full((2, N, max(n, 0)), fill)
+        f = np.full((2, N), -1, np.int32)
+        perm = np.full((2, N, max(n, 0)), -1, np.int32)
+        F = np.zeros((2, N, W))
+        _lib.check(_lib.lib().br_debug_wave_lu(N, n, int(wpb), int(bool(dirty)), _lib.dptr(J0), _lib.dptr(J1), _lib.dptr(g0),
+                                               _lib.dptr(g1), _lib.dptr(b), _lib.iptr(pin), _lib.dptr(x), _lib.iptr(f),
+                                               _lib.iptr(perm), _lib.dptr(F)))
+        return x, f, perm, F
+
     def wave_eval(self, T, Asv, u, T_prev=None, rate_mult=None, rate_mult_row=None):
         """(du, J) as the wavefront integrator of this mechanism evaluates them (br_debug_wave_eval: k_integrate's
         instance width, reactors per workgroup, slots and init_tconst). T_prev [N]: the T-only constants are

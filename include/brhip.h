@@ -382,6 +382,24 @@ int br_sensitivity(br_mech* m, int N, const double* T, const double* Asv, const 
  * x_i = (I - gamma_i J_i)^-1 b_i. J[N][n][n] row-major; fail[i] = 0 or (k+1) for a zero pivot. */
 int br_debug_lu_solve(int N, int n, const double* J, const double* gamma, const double* b, double* x, int* fail);
 
+/* wavefront LU check (tests): the factorization and solve of k_integrate (lu_factor / lu_solve for n <= 64,
+ * lu_factor2 / lu_solve2 for 64 < n <= 72, the instance of n as in a run: 16, 32, 56, 64 or 72 wide) strung
+ * together as the integrator does. Per matrix i, leg A factors I - gamma0_i J0_i with original row perm_in[i][s] loaded
+ * into position s (perm_in NULL: the identity, a reactor's first LU) and solves b_i; leg B factors I - gamma1_i J1_i
+ * (J1 / gamma1 NULL: J0 / gamma0 again) with the rows in leg A's pivot order and solves b_i again. Outputs, leg A
+ * then leg B: x[2][N][n]; fail[2][N] = 0 or (k+1) for a zero pivot -- no solve then, as in a run, and the x entries
+ * keep the caller's values; perm[2][N][n], the original row of each pivot step; F[2][N][W], the factor workspace
+ * after the leg in the device layout, W = nmax * nmax + 64 doubles for nmax <= 64 (column-major M with nmax rows
+ * per column, rows in step order: L below the diagonal, D^-1 U above, 0 on it; then D^-1[64]) and (72 + 1) * 80 for
+ * n > 64 (72 columns of 80 rows, then D^-1[80]). dirty != 0: before leg A every double of the factor workspace,
+ * and in both legs every double of the saved-J block outside rows and columns < n, holds a quiet NaN (in a run the
+ * factor area holds Jacobian scratch). wpb waves per workgroup, 1 .. the integrator's limit for the width (4, or 16 for
+ * 32 < n <= 64, 12 above), each with its own LDS scratch and workspace slot; one workgroup up to N = 4 wpb, two
+ * above, a wave taking matrices slot, slot + waves, ... in the same slot. BR_ERR_INPUT: n outside 1..72, wpb out of
+ * range, a perm_in row that is no permutation of 0..n-1, a NULL array other than J1, gamma1, perm_in. */
+int br_debug_wave_lu(int N, int n, int wpb, int dirty, const double* J0, const double* J1, const double* gamma0,
+                     const double* gamma1, const double* b, const int* perm_in, double* x, int* fail, int* perm, double* F);
+
 /* group-engine check (tests): RHS and analytic Jacobian as the group integrator evaluates them,
  * through the device functions, workgroup shape, LDS blocks and global slots of the instance
  * br_integrate would launch for this mechanism (BR_ERR_UNSUPPORTED when it has none, n > 32). At most

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void k_coop(int N, int n, const double* __rest
                             const double akk = bcast(ak, k);
                             const bool kcand = (__ballot(cand) >> k) & 1ull;
                             const bool fast = kcand && __ballot(cand && lane != k && !(fabs(ak) < fabs(akk))) == 0;
-                            const int p = fast ? k : pivot_lane(ak, cand ? 0x7fffffffu : 0u, prow);
+                            const int p = fast ? k : pivot_lane(ak, cand ? 0x7fffffffu : 0u, prow, pstep, k);
                             const double piv = fast ? akk : bcast(ak, p);
                             const double rinv = 1.0 / piv;
                             const bool isp = lane == p;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_coop(int N, int n, const double* __rest
                             const double akk = bcast(ak, k);
                             const bool kcand = (__ballot(cand) >> k) & 1ull;
                             const bool fast = kcand && __ballot(cand && lane != k && !(fabs(ak) < fabs(akk))) == 0;
-                            const int p = fast ? k : pivot_lane(ak, cand ? 0x7fffffffu : 0u, prow);
+                            const int p = fast ? k : pivot_lane(ak, cand ? 0x7fffffffu : 0u, prow, pstep, k);
                             const double piv = fast ? akk : bcast(ak, p);
                             const double rinv = 1.0 / piv;
                             const bool isp = lane == p;
