@@ -533,39 +533,40 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 
+// The launch geometry of one integrator instance for one mechanism. A shape the mechanism does not have (state < 0)
+// keeps every other field 0, so gl and nm also answer "eligible?".
+struct Shape {
+    int state = 0;       // 0: not looked for yet, 1: has one, -1: has none
+    int gl = 0, nm = 0;  // instance widths: NMAX of k_integrate | GL (16: quad, 32: pair) and NM of k_group | NM of k_lane
+    int threads = 0;     // per workgroup
+    int rpb = 0;         // reactors per workgroup
+    size_t shmem = 0;    // dynamic LDS bytes per workgroup
+    int wg_per_cu = 0;   // resident workgroups per CU
+};
+
 struct br_mech {
     int device = 0;
-    int ng = 0, ns = 0, nrg = 0, nrs = 0, n = 0, nmax = 64, rpb = 1, waves_per_cu = 0;
+    int ng = 0, ns = 0, nrg = 0, nrs = 0, n = 0, nmax = 64;
     DevMech dm{};
     size_t shmem1 = 0;
     std::vector<void*> allocs;   // the uploaded tables
-    size_t shmem = 0;
     DevBuf ws;                   // staging of the host-buffer entry points (Stage)
     DevBuf jws;                  // wavefront engine: per-wave workspace slots (jws_bytes)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_recorded = false;
-    // one-reactor-per-lane engine (brhip_lane.hpp): 0 = not eligible, else the register width NM
-    int lane_nm = 0, lane_blocks = 0;
-    size_t lane_shmem = 0;
-    DevBuf lws;                  // saved Jacobians, slot-major [NM*NM][slots]
+    // the launch shapes, found in br_mech_create: the wavefront engine (always has one; the programme instances
+    // run in it too), the one-reactor-per-lane engine (brhip_lane.hpp) and the group engine (brhip_group.hpp)
+    Shape wave, lane, grp;
+    // ... and those of the energy instances (brhip_energy.hpp), widths from ng + 1, each found at the first look
+    // (energy_shape, group_energy_shape): wavefront (none: too large for the LDS) and group (none: surface species,
+    // ng + 1 > 32, too many efficiency sets, or the LDS)
+    Shape wave_e, grp_e;
+    DevBuf lws;                  // lane engine: saved Jacobians, slot-major [NM*NM][slots]
     DevBuf queue;                // int[2 + DEFER_CAP]: work counter, deferred count, deferred reactors
-    // group engine (brhip_group.hpp): gl = 0 not eligible, else the group width (16: quad, 32: pair)
-    // and the register width NM of k_group<gl, NM>
-    int grp_gl = 0, grp_nm = 0, grp_blocks = 0;
-    size_t grp_shmem = 0;
-    DevBuf qws;                  // saved Jacobians, 16 x 16 per group slot
+    DevBuf qws;                  // group engines: saved Jacobians, 16 x 16 per group slot
     DevBuf wq;                   // int: k_integrate work counter
     DevBuf defer_t0;             // double[DEFER_CAP]: start time of each deferred lane reactor
     int ncu = 0;
-    // energy runs (brhip_energy.hpp): the instance width from ng + 1 and its own launch shape, found at the
-    // first such run (energy_shape); e_nmax = 0: not looked for yet
-    int e_nmax = 0, e_rpb = 0, e_waves_per_cu = 0;
-    size_t e_shmem = 0;
-    // ... on a group engine (k_group<ge_gl, ge_nm, true>, (ge_gl, ge_nm) from ng + 1): its own LDS block, slot size
-    // and occupancy, found at the first look (group_energy_shape); ge_state 0: not looked for yet, 1: has one,
-    // -1: has none (surface species, ng + 1 > 32, too many efficiency sets, or the LDS)
-    int ge_state = 0, ge_gl = 0, ge_nm = 0, ge_blocks = 0;
-    size_t ge_shmem = 0;
     MultBlock* mult_hdr = nullptr;   // the 32 bytes in front of the g_par table (br_opts.rate_mult; brhip_device.hpp)
 };
 
@@ -611,6 +612,45 @@ struct Stage {
     double* push(const double* host, size_t count) { double* d = take(count); put(d, host, count); return d; }
 };
 
+// Workgroups of `threads` threads and `shmem` bytes of dynamic LDS of kernel `fn` that are resident per CU, from the
+// occupancy calculator (VGPRs, LDS); -1 when shmem is over lds_limit or a call fails. Leaves shmem as the
+// kernel's dynamic-LDS attribute.
+static int resident_per_cu(const void* fn, int threads, size_t shmem, size_t lds_limit = LDS_PER_CU, bool whole_granules = true) {
+    if (shmem > lds_limit) return -1;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess) return -1;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, shmem) != hipSuccess) return -1;
+    // the calculator ignores the LDS allocation granule: 3 x 54.5 KB workgroups were reported
+    // resident but only 2 were (measured: 6 of 9 waves/CU); count whole granules per CU
+    if (whole_granules) nb = std::min(nb, (int)(LDS_PER_CU / ((shmem + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
+    return std::max(nb, 0);
+}
+// The shape of a wavefront-engine instance k_integrate<nmax, ...>: the reactors (waves) per workgroup that maximise
+// the resident waves per CU, with lds_bytes(rpb) of LDS (tables once per workgroup + one block per reactor); ties
+// go to the smaller workgroup. None when not even one reactor fits.
+template <class F>
+static Shape wave_shape(const void* kfn, int nmax, F lds_bytes) {
+    Shape best{-1};
+    for (int rpb = 1; rpb <= br_maxrpb(nmax); ++rpb) {
+        const size_t b = lds_bytes(rpb);
+        const int nb = resident_per_cu(kfn, 64 * rpb, b);
+        if (nb < 0) break;
+        if (nb * rpb > best.wg_per_cu * best.rpb) best = Shape{1, 0, nmax, 64 * rpb, rpb, b, nb};
+    }
+    return best;
+}
+// The shape of the group instance (brhip_group.hpp) of a system of nsys equations with nrs surface reactions:
+// 4 reactors per wave for nsys <= 16, 2 for nsys <= 32, BR_QWPB waves per workgroup, k_group<GL, NM, ...> from
+// `kernel` (grp_kernel, grp_energy_kernel). None when nsys or the efficiency sets are too many, or by the LDS.
+static Shape group_shape(const br_mech* m, int nsys, int nrs, const void* (*kernel)(int gl, int nm)) {
+    if (nsys > 32 || m->dm.nset > grp::MAX_SETS) return Shape{-1};
+    const int gl = nsys <= 16 ? 16 : 32, nm = nsys <= 9 ? 9 : (nsys <= 16 ? 16 : (nsys <= 24 ? 24 : 32));
+    const int rpb = BR_QWPB * (64 / gl);
+    const size_t shmem = (size_t)m->dm.img_bytes + (size_t)rpb * grp::block_bytes(gl, nm, m->nrg, m->dm.nfo, nrs);
+    const int nb = resident_per_cu(kernel(gl, nm), 64 * BR_QWPB, shmem);
+    return nb > 0 ? Shape{1, gl, nm, 64 * BR_QWPB, rpb, shmem, nb} : Shape{-1};
+}
+
 extern "C" {
 
 int br_version(void) { return 232; }   // 232: br_debug_wave_lu; 231: br_mech_energy_launch_info, br_debug_group_energy_eval (br_opts as in 230)
@@ -645,36 +685,31 @@ int br_mech_info(const br_mech* m, int* ng, int* ns, int* nrg, int* nrs) {
 static int pick_engine(const br_mech* m) {
     const char* eng = getenv("BRHIP_ENGINE");
     if (eng && strcmp(eng, "wave") == 0) return 0;
-    if (eng && strcmp(eng, "lane") == 0) return m->lane_nm;
-    const int gcode = -(100 * m->grp_gl + m->grp_nm);
-    if (m->grp_gl == 16 && ((eng && strcmp(eng, "quad") == 0) || (!eng && BR_QUAD_DEFAULT))) return gcode;
-    if (m->grp_gl == 32 && ((eng && strcmp(eng, "pair") == 0) || (!eng && BR_PAIR_DEFAULT))) return gcode;
-    return m->lane_nm;
+    if (eng && strcmp(eng, "lane") == 0) return m->lane.nm;
+    const int gcode = -(100 * m->grp.gl + m->grp.nm);
+    if (m->grp.gl == 16 && ((eng && strcmp(eng, "quad") == 0) || (!eng && BR_QUAD_DEFAULT))) return gcode;
+    if (m->grp.gl == 32 && ((eng && strcmp(eng, "pair") == 0) || (!eng && BR_PAIR_DEFAULT))) return gcode;
+    return m->lane.nm;
 }
 int br_mech_engine(const br_mech* m) {
     if (!m) return fail(BR_ERR_INPUT, "null mechanism");
     return pick_engine(m);
 }
 
+// what the launch-info entry points report of a shape (each through its pointer, when given): reactors per
+// workgroup, resident waves per CU, LDS bytes per workgroup, reactors resident on the device
+static void report_shape(const Shape& sh, int ncu, int* rpb, int* waves_per_cu, long long* lds_bytes, int* resident) {
+    if (rpb) *rpb = sh.rpb;
+    if (waves_per_cu) *waves_per_cu = sh.wg_per_cu * (sh.threads / 64);
+    if (lds_bytes) *lds_bytes = (long long)sh.shmem;
+    if (resident) *resident = std::max(ncu, 1) * sh.wg_per_cu * sh.rpb;
+}
+
 int br_mech_launch_info(const br_mech* m, int* rpb, int* waves_per_cu, long long* lds_bytes) {
     if (!m) return fail(BR_ERR_INPUT, "null mechanism");
     // the geometry of the engine br_integrate launches (pick_engine), not always the wavefront one
     const int e = pick_engine(m);
-    const int ncu = m->ncu > 0 ? m->ncu : 1;
-    int r = m->rpb, w = m->waves_per_cu;
-    long long l = (long long)m->shmem;
-    if (e < 0) {          // group engine: BR_QWPB waves per workgroup, 64 / GL reactors per wave
-        r = BR_QWPB * (64 / m->grp_gl);
-        w = m->grp_blocks / ncu * BR_QWPB;
-        l = (long long)m->grp_shmem;
-    } else if (e > 0) {   // reactor-per-lane engine: one wave of 64 reactors per workgroup
-        r = 64;
-        w = m->lane_blocks / ncu;
-        l = (long long)m->lane_shmem;
-    }
-    if (rpb) *rpb = r;
-    if (waves_per_cu) *waves_per_cu = w;
-    if (lds_bytes) *lds_bytes = l;
+    report_shape(e < 0 ? m->grp : e > 0 ? m->lane : m->wave, m->ncu, rpb, waves_per_cu, lds_bytes, nullptr);
     return 0;
 }
 
@@ -717,56 +752,20 @@ int br_mech_create(const br_mech_desc* d, int device, br_mech** out) {
     rc |= upload(m, pk.tb_eff, &M.tb_eff); rc |= upload(m, pk.col_ptr, &M.col_ptr); rc |= upload(m, pk.col_rx, &M.col_rx);
     if (rc) return rc;
     HIPCHK(hipDeviceGetAttribute(&m->ncu, hipDeviceAttributeMultiprocessorCount, device));
-    // ---- reactors (waves) per workgroup: the value that maximises resident waves per CU,
-    //      from the occupancy calculator (VGPRs, LDS: tables once per workgroup + one block
-    //      per reactor); ties go to the smaller workgroup
-    const void* kfn = wave_kernel(m->nmax);
-    int best = 0, best_w = 0;
-    for (int rpb = 1; rpb <= br_maxrpb(m->nmax); ++rpb) {
-        const size_t b = wg_lds_bytes(M, rpb);
-        if (b > LDS_PER_CU) break;
-        if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b) != hipSuccess) break;
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 64 * rpb, b) != hipSuccess) break;
-        // the calculator ignores the LDS allocation granule: 3 x 54.5 KB workgroups were reported
-        // resident but only 2 were (measured: 6 of 9 waves/CU); count whole granules per CU
-        nb = std::min(nb, (int)(LDS_PER_CU / ((b + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
-        if (nb * rpb > best_w) { best_w = nb * rpb; best = rpb; }
-    }
-    if (best_w == 0) return fail(BR_ERR_UNSUPPORTED, "mechanism too large for LDS");
-    m->rpb = best;
-    m->waves_per_cu = best_w;
-    m->shmem = wg_lds_bytes(M, best);
+    // ---- the launch shapes (the energy instances': at the first look)
+    m->wave = wave_shape(wave_kernel(m->nmax), m->nmax, [&](int rpb) { return wg_lds_bytes(M, rpb); });
+    if (m->wave.state < 0) return fail(BR_ERR_UNSUPPORTED, "mechanism too large for LDS");
     m->shmem1 = wg_lds_bytes(M, 1);
-    // ---- one-reactor-per-lane engine for small gas-only mechanisms (brhip_lane.hpp)
+    // one-reactor-per-lane engine for small gas-only mechanisms (brhip_lane.hpp): one wave of 64 reactors per
+    // workgroup, at most 64 KB of LDS, residency as the calculator gives it (no granule count)
+    m->lane.state = -1;
     if (ns == 0 && n <= 12) {
-        m->lane_nm = n <= 9 ? 9 : 12;
-        const void* lfn = lane_kernel(m->lane_nm);
-        m->lane_shmem = lane_lds_bytes(m->lane_nm, n, M.nset, nrg, M.nfo);
-        int nb = 0;
-        if (m->lane_shmem > 64 * 1024 ||
-            hipFuncSetAttribute(lfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lane_shmem) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, lfn, 64, m->lane_shmem) != hipSuccess || nb <= 0)
-            m->lane_nm = 0;   // does not fit: the wave engine integrates it
-        else
-            m->lane_blocks = nb * m->ncu;
+        const int nm = n <= 9 ? 9 : 12;
+        const size_t shmem = lane_lds_bytes(nm, n, M.nset, nrg, M.nfo);
+        const int nb = resident_per_cu(lane_kernel(nm), 64, shmem, 64 * 1024, false);
+        if (nb > 0) m->lane = Shape{1, 0, nm, 64, 64, shmem, nb};   // (else it does not fit: the wave engine integrates it)
     }
-    // ---- group engines (brhip_group.hpp): 4 reactors per wave for n <= 16, 2 for n <= 32
-    if (n <= 32 && M.nset <= grp::MAX_SETS) {
-        m->grp_gl = n <= 16 ? 16 : 32;
-        m->grp_nm = n <= 9 ? 9 : (n <= 16 ? 16 : (n <= 24 ? 24 : 32));
-        const void* gfn = grp_kernel(m->grp_gl, m->grp_nm);
-        m->grp_shmem = (size_t)M.img_bytes + (size_t)BR_QWPB * (64 / m->grp_gl) * grp::block_bytes(m->grp_gl, m->grp_nm, nrg, M.nfo, nrs);
-        int nb = 0;
-        if (m->grp_shmem > LDS_PER_CU ||
-            hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->grp_shmem) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gfn, 64 * BR_QWPB, m->grp_shmem) != hipSuccess || nb <= 0) {
-            m->grp_gl = m->grp_nm = 0;
-        } else {
-            nb = std::min(nb, (int)(LDS_PER_CU / ((m->grp_shmem + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
-            m->grp_blocks = nb * m->ncu;
-        }
-    }
+    m->grp = group_shape(m, n, nrs, grp_kernel);
     HIPCHK(hipEventCreate(&m->ev0));
     HIPCHK(hipEventCreate(&m->ev1));
     *out = owner.release();
@@ -997,47 +996,20 @@ static int energy_shape(br_mech* m) {
     if (m->ng + 1 > 56)
         return fail(BR_ERR_UNSUPPORTED, "br_opts.energy: ng + 1 = " + std::to_string(m->ng + 1) +
                                             " components exceed the 56 of the widest energy instance");
-    if (m->e_nmax) return 0;
-    const int nmax = nmax_of(m->ng + 1);
-    const void* kfn = wave_energy_kernel(nmax);
-    int best = 0, best_w = 0;
-    for (int rpb = 1; rpb <= br_maxrpb(nmax); ++rpb) {
-        const size_t b = energy_wg_lds_bytes(m->dm, nmax, rpb);
-        if (b > LDS_PER_CU) break;
-        if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b) != hipSuccess) break;
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 64 * rpb, b) != hipSuccess) break;
-        nb = std::min(nb, (int)(LDS_PER_CU / ((b + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
-        if (nb * rpb > best_w) { best_w = nb * rpb; best = rpb; }
+    if (!m->wave_e.state) {
+        const int nmax = nmax_of(m->ng + 1);
+        m->wave_e = wave_shape(wave_energy_kernel(nmax), nmax, [&](int rpb) { return energy_wg_lds_bytes(m->dm, nmax, rpb); });
     }
-    if (best_w == 0) return fail(BR_ERR_UNSUPPORTED, "br_opts.energy: mechanism too large for LDS");
-    m->e_rpb = best;
-    m->e_waves_per_cu = best_w;
-    m->e_shmem = energy_wg_lds_bytes(m->dm, nmax, best);
-    m->e_nmax = nmax;
+    if (m->wave_e.state < 0) return fail(BR_ERR_UNSUPPORTED, "br_opts.energy: mechanism too large for LDS");
     return 0;
 }
 
 // the group energy instance of a mechanism (brhip_group.hpp, k_group<GL, NM, true>): (GL, NM) from nsys = ng + 1,
-// one shape up from the isothermal instance where ng = 9, 16 or 24; its LDS block and resident workgroups from the
-// occupancy calculator on that kernel, kept in the handle. Returns whether the mechanism has one.
+// one shape up from the isothermal instance where ng = 9, 16 or 24; its own LDS block and residency, kept in
+// the handle. Returns whether the mechanism has one.
 static bool group_energy_shape(br_mech* m) {
-    if (m->ge_state) return m->ge_state > 0;
-    m->ge_state = -1;
-    const int nsys = m->ng + 1;
-    if (m->ns > 0 || nsys > 32 || m->dm.nset > grp::MAX_SETS) return false;
-    const int gl = nsys <= 16 ? 16 : 32, nm = nsys <= 9 ? 9 : (nsys <= 16 ? 16 : (nsys <= 24 ? 24 : 32));
-    const void* gfn = grp_energy_kernel(gl, nm);
-    const size_t shmem = (size_t)m->dm.img_bytes + (size_t)BR_QWPB * (64 / gl) * grp::block_bytes(gl, nm, m->nrg, m->dm.nfo, 0);
-    int nb = 0;
-    if (shmem > LDS_PER_CU || hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gfn, 64 * BR_QWPB, shmem) != hipSuccess || nb <= 0)
-        return false;
-    nb = std::min(nb, (int)(LDS_PER_CU / ((shmem + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE)));
-    m->ge_gl = gl; m->ge_nm = nm; m->ge_shmem = shmem;
-    m->ge_blocks = nb * std::max(m->ncu, 1);
-    m->ge_state = 1;
-    return true;
+    if (!m->grp_e.state) m->grp_e = m->ns > 0 ? Shape{-1} : group_shape(m, m->ng + 1, 0, grp_energy_kernel);
+    return m->grp_e.state > 0;
 }
 // engine of an energy run (codes of br_mech_engine): the group energy instance when BRHIP_ENGINE asks for the
 // group width ng + 1 selects (quad: ng + 1 <= 16, pair: 16 < ng + 1 <= 32) and the mechanism has one; in every
@@ -1049,7 +1021,7 @@ static int pick_energy_engine(br_mech* m) {
     const int nsys = m->ng + 1;
     const bool quad = strcmp(eng, "quad") == 0 && nsys <= 16, pair = strcmp(eng, "pair") == 0 && nsys > 16 && nsys <= 32;
     if (!(quad || pair) || !group_energy_shape(m)) return 0;
-    return -(100 * m->ge_gl + m->ge_nm);
+    return -(100 * m->grp_e.gl + m->grp_e.nm);
 }
 
 // the kernel options of a run: br_opts with its defaults filled in (no work list, no deferral)
@@ -1075,39 +1047,83 @@ static KOpts make_kopts(const br_mech* m, const br_opts* opts, bool traced) {
     return o;
 }
 
-// k_integrate on `nwg` workgroups of m->rpb reactors (waves) each
-// (prog: a temperature-programme run, the k_integrate<NMAX, true> instance with KOptsProg = o + the block)
-static int launch_wave(br_mech* m, const DevMech& dm, int N, int nwg, const double* dT, const double* dAsv, double* du,
-                       const double* dtf, const KOpts& o, br_stats* dstats, double* trace, hipStream_t s,
-                       const TProg* prog = nullptr) {
-    const void* fn = prog ? wave_tprog_kernel(m->nmax) : wave_kernel(m->nmax);
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->shmem));
-    const int rpb = m->rpb;
+// The instance families of a run. The kernel options of each begin with the run's KOpts: ISOTHERMAL takes KOpts
+// itself, PROGRAMME KOptsProg (+ the programme block), ENERGY KOptsEnergy (+ the T outputs).
+enum Flavour { ISOTHERMAL, PROGRAMME, ENERGY };
+static KOptsEnergy energy_kopts(const KOpts& o, const br_opts* opts) {
+    KOptsEnergy oe;
+    static_cast<KOpts&>(oe) = o;
+    oe.T_end = opts->T_end;
+    oe.T_out = o.nout ? opts->T_out : nullptr;
+    return oe;
+}
+
+// k_integrate of flavour `fl` and shape `sh` on `nwg` workgroups of sh.rpb reactors (waves) each
+// (opts: read for a programme's block and an energy run's T outputs only)
+static int launch_wave(br_mech* m, Flavour fl, const Shape& sh, const DevMech& dm, int N, int nwg, const double* dT,
+                       const double* dAsv, double* du, const double* dtf, const KOpts& o, const br_opts* opts,
+                       br_stats* dstats, double* trace, hipStream_t s) {
+    const void* fn = fl == PROGRAMME ? wave_tprog_kernel(sh.nm) : fl == ENERGY ? wave_energy_kernel(sh.nm) : wave_kernel(sh.nm);
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.shmem));
+    const int rpb = sh.rpb;
     double* jws = m->jws.as<double>();
     KOptsProg op;
-    static_cast<KOpts&>(op) = o;
-    if (prog) op.prog = *prog;
+    KOptsEnergy oe;
+    const void* ko = &o;
+    if (fl == PROGRAMME) {
+        static_cast<KOpts&>(op) = o;
+        op.prog = TProg{opts->tprog_t, opts->tprog_T, opts->tprog_row, opts->ntprog, 0};
+        ko = &op;
+    } else if (fl == ENERGY) {
+        oe = energy_kopts(o, opts);
+        ko = &oe;
+    }
     void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf,
-                    prog ? (void*)&op : (void*)&o, (void*)&dstats, (void*)&jws, (void*)&trace};
-    HIPCHK(hipLaunchKernel(fn, dim3(nwg), dim3(64 * rpb), args, m->shmem, s));
+                    (void*)ko, (void*)&dstats, (void*)&jws, (void*)&trace};
+    HIPCHK(hipLaunchKernel(fn, dim3(nwg), dim3(64 * rpb), args, sh.shmem, s));
     return 0;
 }
 
-// k_integrate<NMAX, false, true> of an energy run on `nwg` workgroups of m->e_rpb reactors each
-static int launch_wave_energy(br_mech* m, const DevMech& dm, int N, int nwg, const double* dT, const double* dAsv, double* du,
-                              const double* dtf, const KOpts& o, double* T_end, double* T_out, br_stats* dstats, hipStream_t s) {
-    const void* fn = wave_energy_kernel(m->e_nmax);
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->e_shmem));
-    const int rpb = m->e_rpb;
-    double* jws = m->jws.as<double>();
-    double* trace = nullptr;
-    KOptsEnergy oe;
-    static_cast<KOpts&>(oe) = o;
-    oe.T_end = T_end;
-    oe.T_out = o.nout ? T_out : nullptr;
-    void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf,
-                    (void*)&oe, (void*)&dstats, (void*)&jws, (void*)&trace};
-    HIPCHK(hipLaunchKernel(fn, dim3(nwg), dim3(64 * rpb), args, m->e_shmem, s));
+// The wavefront engine's run. Persistent grid: as many workgroups as are resident at once, reactors from a work
+// counter (BRHIP_STATIC=1: one reactor per wave over ceil(N / rpb) workgroups).
+static int launch_wave_grid(br_mech* m, Flavour fl, const Shape& sh, const DevMech& dm, int N, const double* dT,
+                            const double* dAsv, double* du, const double* dtf, KOpts o, const br_opts* opts,
+                            br_stats* dstats, double* trace, hipStream_t s) {
+    const int rpb = sh.rpb;
+    const char* st_env = getenv("BRHIP_STATIC");
+    const bool dyn = !(st_env && atoi(st_env) == 1) && m->ncu > 0;
+    const int nwg_all = (N + rpb - 1) / rpb;
+    const int nwg = dyn ? std::min(nwg_all, m->ncu * sh.wg_per_cu) : nwg_all;
+    HIPCHK(m->jws.ensure(jws_bytes(m, nwg * rpb)));   // (slots of the 64-wide layout: no narrower than an energy instance's)
+    if (dyn) {
+        HIPCHK(m->wq.ensure(sizeof(int)));
+        HIPCHK(hipMemsetAsync(m->wq.p, 0, sizeof(int), s));
+        o.work = m->wq.as<int>();
+    }
+    HIPCHK(hipEventRecord(m->ev0, s));
+    if (const int rc = launch_wave(m, fl, sh, dm, N, nwg, dT, dAsv, du, dtf, o, opts, dstats, trace, s)) return rc;
+    HIPCHK(hipEventRecord(m->ev1, s));
+    m->ev_recorded = true;
+    return 0;
+}
+
+// A group engine's run on instance `gfn` of shape `sh`: 2 or 4 reactors per wave (one per 32- / 16-lane group),
+// persistent grid over the resident workgroups, reactors from a work counter, m->qws sized by the instance's slot.
+// `o`: the instance's options, KOpts or the KOptsEnergy that begins with it (the kernel reads the whole struct).
+static int launch_group(br_mech* m, const Shape& sh, const void* gfn, const DevMech& dm, int N, const double* dT,
+                        const double* dAsv, double* du, const double* dtf, KOpts* o, br_stats* dstats, hipStream_t s) {
+    const int blocks = std::max(1, std::min((N + sh.rpb - 1) / sh.rpb, sh.wg_per_cu * std::max(m->ncu, 1)));
+    HIPCHK(m->qws.ensure((size_t)blocks * sh.rpb * grp::slot_doubles(sh.gl, m->nrg) * sizeof(double)));
+    HIPCHK(m->queue.ensure((2 + DEFER_CAP) * sizeof(int)));
+    HIPCHK(hipMemsetAsync(m->queue.p, 0, 2 * sizeof(int), s));
+    o->work = m->queue.as<int>();
+    HIPCHK(hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.shmem));
+    HIPCHK(hipEventRecord(m->ev0, s));
+    double* qws = m->qws.as<double>();
+    void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf, (void*)o, (void*)&dstats, (void*)&qws};
+    HIPCHK(hipLaunchKernel(gfn, dim3(blocks), dim3(sh.threads), args, sh.shmem, s));
+    HIPCHK(hipEventRecord(m->ev1, s));
+    m->ev_recorded = true;
     return 0;
 }
 
@@ -1116,21 +1132,8 @@ int br_mech_energy_launch_info(br_mech* m, int* engine, int* rpb, int* waves_per
     HIPCHK(hipSetDevice(m->device));
     if (const int rc = energy_shape(m)) return rc;
     const int e = pick_energy_engine(m);
-    const int ncu = m->ncu > 0 ? m->ncu : 1;
-    // wavefront energy instance: e_rpb reactors (waves) per workgroup, the persistent grid of integrate_dev
-    int r = m->e_rpb, w = m->e_waves_per_cu, res = ncu * (m->e_waves_per_cu / m->e_rpb) * m->e_rpb;
-    long long l = (long long)m->e_shmem;
-    if (e < 0) {   // group energy instance: BR_QWPB waves per workgroup, 64 / GL reactors per wave
-        r = BR_QWPB * (64 / m->ge_gl);
-        w = m->ge_blocks / ncu * BR_QWPB;
-        l = (long long)m->ge_shmem;
-        res = m->ge_blocks * r;
-    }
     if (engine) *engine = e;
-    if (rpb) *rpb = r;
-    if (waves_per_cu) *waves_per_cu = w;
-    if (lds_bytes) *lds_bytes = l;
-    if (resident) *resident = res;
+    report_shape(e < 0 ? m->grp_e : m->wave_e, m->ncu, rpb, waves_per_cu, lds_bytes, resident);
     return 0;
 }
 
@@ -1157,78 +1160,21 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
         HIPCHK(hipGetLastError());
         dm.g_par = reinterpret_cast<const double*>(reinterpret_cast<size_t>(dm.g_par) | 1u);
     }
-    if (energy) {
-        o.dq_jac = 1;   // CVODE's DQ Jacobian, in either engine
-        if (pick_energy_engine(m) < 0) {
-            // the group launch (below) on the energy instance and its shape: persistent grid over the resident
-            // workgroups, reactors from a work counter, m->qws sized by the energy instance's slot
-            const int GL = m->ge_gl;
-            const int gpb = BR_QWPB * (64 / GL);
-            const int blocks = std::max(1, std::min((N + gpb - 1) / gpb, m->ge_blocks));
-            HIPCHK(m->qws.ensure((size_t)blocks * gpb * grp::slot_doubles(GL, m->nrg) * sizeof(double)));
-            HIPCHK(m->queue.ensure((2 + DEFER_CAP) * sizeof(int)));
-            HIPCHK(hipMemsetAsync(m->queue.p, 0, 2 * sizeof(int), s));
-            KOptsEnergy oe;
-            static_cast<KOpts&>(oe) = o;
-            oe.work = m->queue.as<int>();
-            oe.T_end = opts->T_end;
-            oe.T_out = o.nout ? opts->T_out : nullptr;
-            const void* gfn = grp_energy_kernel(GL, m->ge_nm);
-            HIPCHK(hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->ge_shmem));
-            HIPCHK(hipEventRecord(m->ev0, s));
-            double* qws = m->qws.as<double>();
-            void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf, (void*)&oe, (void*)&dstats, (void*)&qws};
-            HIPCHK(hipLaunchKernel(gfn, dim3(blocks), dim3(64 * BR_QWPB), args, m->ge_shmem, s));
-            HIPCHK(hipEventRecord(m->ev1, s));
-            m->ev_recorded = true;
-            return 0;
-        }
-        // the wavefront engine's persistent grid (below) on the energy instance and its shape
-        const int rpb = m->e_rpb;
-        const char* st_env = getenv("BRHIP_STATIC");
-        const bool dyn = !(st_env && atoi(st_env) == 1) && m->ncu > 0 && m->e_waves_per_cu >= rpb;
-        const int nwg_all = (N + rpb - 1) / rpb;
-        const int nwg = dyn ? std::min(nwg_all, m->ncu * (m->e_waves_per_cu / rpb)) : nwg_all;
-        HIPCHK(m->jws.ensure(jws_bytes(m, nwg * rpb)));   // (slots of the 64-wide layout: no narrower than e_nmax's)
-        if (dyn) {
-            HIPCHK(m->wq.ensure(sizeof(int)));
-            HIPCHK(hipMemsetAsync(m->wq.p, 0, sizeof(int), s));
-            o.work = m->wq.as<int>();
-        }
-        HIPCHK(hipEventRecord(m->ev0, s));
-        if (const int rc = launch_wave_energy(m, dm, N, nwg, dT, dAsv, du, dtf, o, opts->T_end, opts->T_out, dstats, s)) return rc;
-        HIPCHK(hipEventRecord(m->ev1, s));
-        m->ev_recorded = true;
-        return 0;
+    if (energy) o.dq_jac = 1;   // CVODE's DQ Jacobian, in either engine
+    // the engine (traced and programme runs: the wavefront engine) and the instance family
+    const int engine = energy ? pick_energy_engine(m) : (trace || prog) ? 0 : pick_engine(m);
+    const Flavour fl = energy ? ENERGY : prog ? PROGRAMME : ISOTHERMAL;
+    if (engine < 0 && energy) {
+        KOptsEnergy oe = energy_kopts(o, opts);
+        return launch_group(m, m->grp_e, grp_energy_kernel(m->grp_e.gl, m->grp_e.nm), dm, N, dT, dAsv, du, dtf, &oe, dstats, s);
     }
-    const int engine = (trace || prog) ? 0 : pick_engine(m);   // traced and programme runs: the wavefront engine
-    const TProg tp = prog ? TProg{opts->tprog_t, opts->tprog_T, opts->tprog_row, opts->ntprog, 0} : TProg{};
-    if (engine < 0) {
-        // 2 or 4 reactors per wave (one per 32- / 16-lane group), persistent grid over the resident
-        // workgroups, reactors from a work counter
-        const int GL = m->grp_gl;
-        const int gpb = BR_QWPB * (64 / GL);
-        const int blocks = std::max(1, std::min((N + gpb - 1) / gpb, m->grp_blocks));
-        HIPCHK(m->qws.ensure((size_t)blocks * gpb * grp::slot_doubles(GL, m->nrg) * sizeof(double)));
-        HIPCHK(m->queue.ensure((2 + DEFER_CAP) * sizeof(int)));
-        HIPCHK(hipMemsetAsync(m->queue.p, 0, 2 * sizeof(int), s));
-        o.work = m->queue.as<int>();
-        const void* gfn = grp_kernel(GL, m->grp_nm);
-        HIPCHK(hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->grp_shmem));
-        HIPCHK(hipEventRecord(m->ev0, s));
-        double* qws = m->qws.as<double>();
-        void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&dAsv, (void*)&du, (void*)&dtf, (void*)&o, (void*)&dstats, (void*)&qws};
-        HIPCHK(hipLaunchKernel(gfn, dim3(blocks), dim3(64 * BR_QWPB), args, m->grp_shmem, s));
-        HIPCHK(hipEventRecord(m->ev1, s));
-        m->ev_recorded = true;
-        return 0;
-    }
+    if (engine < 0) return launch_group(m, m->grp, grp_kernel(m->grp.gl, m->grp.nm), dm, N, dT, dAsv, du, dtf, &o, dstats, s);
     if (engine > 0) {
         // one reactor per lane; reactors still running after defer_steps steps (a few per 1e4 on
         // H2/O2, some of them up to max_steps) are handed to a follow-up wavefront pass, whose
         // per-step latency for a lone reactor is far lower than a wave's with one live lane
-        const int NM = m->lane_nm;
-        const int blocks = std::max(1, std::min((N + 63) / 64, m->lane_blocks));
+        const int NM = m->lane.nm;
+        const int blocks = std::max(1, std::min((N + 63) / 64, m->lane.wg_per_cu * m->ncu));
         const size_t need = (size_t)lane_lay(NM, m->n, m->dm.nset, m->nrg, m->dm.nfo).g_rows * blocks * 64 * sizeof(double);
         if (need >= 0x7fffffffull) return fail(BR_ERR_UNSUPPORTED, "lane workspace exceeds the 2 GB buffer range");
         HIPCHK(m->lws.ensure(need));
@@ -1242,45 +1188,28 @@ static int integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv
         HIPCHK(hipMemsetAsync(m->queue.p, 0, 2 * sizeof(int), s));
         HIPCHK(hipEventRecord(m->ev0, s));
         const void* lfn = lane_kernel(NM);
-        HIPCHK(hipFuncSetAttribute(lfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lane_shmem));
+        HIPCHK(hipFuncSetAttribute(lfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lane.shmem));
         double* lws = m->lws.as<double>();
         int* queue = m->queue.as<int>();
         double* defer_t0 = m->defer_t0.as<double>();
         void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&du, (void*)&dtf, (void*)&o, (void*)&dstats, (void*)&lws,
                         (void*)&queue, (void*)&defer_t0, (void*)&cap};
-        HIPCHK(hipLaunchKernel(lfn, dim3(blocks), dim3(64), args, m->lane_shmem, s));
+        HIPCHK(hipLaunchKernel(lfn, dim3(blocks), dim3(64), args, m->lane.shmem, s));
         if (o.defer_steps < o.max_steps) {   // the deferred reactors continue on the wavefront engine
             KOpts o2 = o;
             o2.defer_steps = o.max_steps;
             o2.rid_list = queue + 2;
             o2.rid_count = queue + 1;
             o2.rid_t0 = defer_t0;
-            const int rc = launch_wave(m, dm, cap, (cap + m->rpb - 1) / m->rpb, dT, dAsv, du, dtf, o2, dstats, nullptr, s);
-            if (rc) return rc;
+            const int nwg = (cap + m->wave.rpb - 1) / m->wave.rpb;
+            if (const int rc = launch_wave(m, ISOTHERMAL, m->wave, dm, cap, nwg, dT, dAsv, du, dtf, o2, nullptr, dstats, nullptr, s))
+                return rc;
         }
         HIPCHK(hipEventRecord(m->ev1, s));
         m->ev_recorded = true;
         return 0;
     }
-    const int rpb = m->rpb;
-    // persistent grid: as many workgroups as are resident at once, reactors from a work counter
-    // (BRHIP_STATIC=1: one reactor per wave over ceil(N / rpb) workgroups)
-    const char* st_env = getenv("BRHIP_STATIC");
-    const bool dyn = !(st_env && atoi(st_env) == 1) && m->ncu > 0 && m->waves_per_cu >= rpb;
-    const int nwg_all = (N + rpb - 1) / rpb;
-    const int nwg = dyn ? std::min(nwg_all, m->ncu * (m->waves_per_cu / rpb)) : nwg_all;
-    HIPCHK(m->jws.ensure(jws_bytes(m, nwg * rpb)));
-    if (dyn) {
-        HIPCHK(m->wq.ensure(sizeof(int)));
-        HIPCHK(hipMemsetAsync(m->wq.p, 0, sizeof(int), s));
-        o.work = m->wq.as<int>();
-    }
-    HIPCHK(hipEventRecord(m->ev0, s));
-    const int rc = launch_wave(m, dm, N, nwg, dT, dAsv, du, dtf, o, dstats, trace, s, prog ? &tp : nullptr);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(m->ev1, s));
-    m->ev_recorded = true;
-    return 0;
+    return launch_wave_grid(m, fl, energy ? m->wave_e : m->wave, dm, N, dT, dAsv, du, dtf, o, opts, dstats, trace, s);
 }
 
 int br_integrate_dev(br_mech* m, int N, const double* dT, const double* dAsv, double* du, const double* dtf,

@@ -330,10 +330,9 @@ __global__ __launch_bounds__(64 * BR_QWPB) void k_group_lu(int N, int n, const d
 extern "C" int br_debug_group_eval(br_mech* m, int N, const double* T, const double* Asv, const double* u, double* du,
                                    double* J) {
     if (!m || N <= 0 || !T || !u || !du || !J) return fail(BR_ERR_INPUT, "bad argument");
-    if (!m->grp_gl) return fail(BR_ERR_UNSUPPORTED, "mechanism is not eligible for a group engine");
+    if (!m->grp.gl) return fail(BR_ERR_UNSUPPORTED, "mechanism is not eligible for a group engine");
     HIPCHK(hipSetDevice(m->device));
-    const int n = m->n, GL = m->grp_gl, NM = m->grp_nm;
-    const int gpb = BR_QWPB * (64 / GL);
+    const int n = m->n, GL = m->grp.gl, NM = m->grp.nm, gpb = m->grp.rpb;
     const int blocks = std::min(2, (N + gpb - 1) / gpb);                // small fixed grid: the groups reuse their slots
     double *dT, *dA, *du_, *ddu, *dJ, *dws;
     DevScratch S;
@@ -347,11 +346,11 @@ extern "C" int br_debug_group_eval(br_mech* m, int N, const double* T, const dou
     if (Asv) HIPCHK(hipMemcpy(dA, Asv, (size_t)N * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
     const void* fn = grp_instance(GL, NM, [](auto g, auto w) { return (const void*)k_group_eval<g(), w()>; });
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->grp_shmem));
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->grp.shmem));
     const DevMech dm = m->dm;
     const double* pA = Asv ? dA : nullptr;
     void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&pA, (void*)&du_, (void*)&ddu, (void*)&dJ, (void*)&dws};
-    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * BR_QWPB), args, m->grp_shmem, 0));
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(m->grp.threads), args, m->grp.shmem, 0));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(J, dJ, (size_t)N * n * n * 8, hipMemcpyDeviceToHost));
@@ -658,9 +657,9 @@ static const void* wave_eval_kernel(int nmax) {
 extern "C" int br_debug_lane_eval(br_mech* m, int N, const double* T, const double* u, int nmult, const double* rate_mult,
                                   const int* rate_mult_row, double* du, double* J) {
     if (!m || N <= 0 || !T || !u || !du || !J) return fail(BR_ERR_INPUT, "bad argument");
-    if (!m->lane_nm) return fail(BR_ERR_UNSUPPORTED, "mechanism is not eligible for the lane engine");
+    if (!m->lane.nm) return fail(BR_ERR_UNSUPPORTED, "mechanism is not eligible for the lane engine");
     HIPCHK(hipSetDevice(m->device));
-    const int n = m->n, NM = m->lane_nm;
+    const int n = m->n, NM = m->lane.nm;
     // small fixed grid: one workgroup up to 128 reactors, else two, so that lanes take a second reactor in
     // the rows of their first from N = 65 on (N = 100: lanes 0..35 of the one workgroup; N >= 192: every lane)
     const int blocks = std::min(2, (N + 127) / 128);
@@ -678,9 +677,9 @@ extern "C" int br_debug_lane_eval(br_mech* m, int N, const double* T, const doub
     HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
     const void* fn = lane_eval_kernel(NM);
     if (!fn) return fail(BR_ERR_UNSUPPORTED, "no lane check kernel of this width");
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lane_shmem));
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lane.shmem));
     void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dJ, (void*)&dws};
-    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64), args, m->lane_shmem, 0));
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64), args, m->lane.shmem, 0));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(J, dJ, (size_t)N * n * n * 8, hipMemcpyDeviceToHost));
@@ -727,7 +726,7 @@ extern "C" int br_debug_wave_eval(br_mech* m, int N, const double* T, const doub
                                   int nmult, const double* rate_mult, const int* rate_mult_row, double* du, double* J) {
     if (!m || N <= 0 || !T || !u || !du || !J) return fail(BR_ERR_INPUT, "bad argument");
     HIPCHK(hipSetDevice(m->device));
-    const int n = m->n, rpb = m->rpb;
+    const int n = m->n, rpb = m->wave.rpb;
     // small fixed grid: one workgroup up to 4 rpb reactors, else two, so that every wave takes a second
     // reactor in the slot of its first from N = 2 rpb (one workgroup) or 4 rpb (two) on
     const int blocks = std::min(2, (N + 4 * rpb - 1) / (4 * rpb));
@@ -750,11 +749,11 @@ extern "C" int br_debug_wave_eval(br_mech* m, int N, const double* T, const doub
     }
     const void* fn = wave_eval_kernel(m->nmax);
     if (!fn) return fail(BR_ERR_UNSUPPORTED, "no wavefront check kernel of this width");
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->shmem));
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->wave.shmem));
     const double* pA = Asv ? dA : nullptr;
     void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&pA, (void*)&du_, (void*)&dTp, (void*)&ddu, (void*)&dJ,
                     (void*)&dws};
-    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->shmem, 0));
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->wave.shmem, 0));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(J, dJ, (size_t)N * n * n * 8, hipMemcpyDeviceToHost));
@@ -766,7 +765,7 @@ extern "C" int br_debug_energy_eval(br_mech* m, int N, const double* T, const do
     if (!m || N <= 0 || !T || !u || !du) return fail(BR_ERR_INPUT, "bad argument");
     HIPCHK(hipSetDevice(m->device));
     if (const int rc = energy_shape(m)) return rc;
-    const int n = m->n, rpb = m->e_rpb;
+    const int n = m->n, rpb = m->wave_e.rpb, nmax = m->wave_e.nm;
     const int blocks = std::min(2, (N + 4 * rpb - 1) / (4 * rpb));   // (as br_debug_wave_eval)
     double *dT, *du_, *ddu, *dws;
     DevScratch S;
@@ -775,14 +774,14 @@ extern "C" int br_debug_energy_eval(br_mech* m, int N, const double* T, const do
     HIPCHK(S.alloc(&dT, (size_t)N * 8));
     HIPCHK(S.alloc(&du_, (size_t)N * n * 8));
     HIPCHK(S.alloc(&ddu, (size_t)N * (n + 1) * 8));
-    HIPCHK(S.alloc(&dws, (size_t)blocks * rpb * ws_doubles(m->e_nmax, m->nrg) * 8));
+    HIPCHK(S.alloc(&dws, (size_t)blocks * rpb * ws_doubles(nmax, m->nrg) * 8));
     HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
-    const void* fn = energy_eval_kernel(m->e_nmax);
+    const void* fn = energy_eval_kernel(nmax);
     if (!fn) return fail(BR_ERR_UNSUPPORTED, "no energy check kernel of this width");
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->e_shmem));
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->wave_e.shmem));
     void* args[] = {(void*)&dm, (void*)&N, (void*)&rpb, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dws};
-    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->e_shmem, 0));
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * rpb), args, m->wave_e.shmem, 0));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * (n + 1) * 8, hipMemcpyDeviceToHost));
     return 0;
@@ -794,8 +793,7 @@ extern "C" int br_debug_group_energy_eval(br_mech* m, int N, const double* T, co
     HIPCHK(hipSetDevice(m->device));
     if (!group_energy_shape(m))
         return fail(BR_ERR_UNSUPPORTED, "mechanism has no group energy instance (gas-only, ng + 1 <= 32, <= 32 efficiency sets)");
-    const int n = m->n, GL = m->ge_gl, NM = m->ge_nm;
-    const int gpb = BR_QWPB * (64 / GL);
+    const int n = m->n, GL = m->grp_e.gl, NM = m->grp_e.nm, gpb = m->grp_e.rpb;
     const int blocks = std::min(2, (N + gpb - 1) / gpb);                // small fixed grid: the groups reuse their slots
     double *dT, *du_, *ddu, *dws;
     DevScratch S;
@@ -808,9 +806,9 @@ extern "C" int br_debug_group_energy_eval(br_mech* m, int N, const double* T, co
     HIPCHK(hipMemcpy(dT, T, (size_t)N * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(du_, u, (size_t)N * n * 8, hipMemcpyHostToDevice));
     const void* fn = grp_instance(GL, NM, [](auto g, auto w) { return (const void*)k_group_energy_eval<g(), w()>; });
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->ge_shmem));
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->grp_e.shmem));
     void* args[] = {(void*)&dm, (void*)&N, (void*)&dT, (void*)&du_, (void*)&ddu, (void*)&dws};
-    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(64 * BR_QWPB), args, m->ge_shmem, 0));
+    HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(m->grp_e.threads), args, m->grp_e.shmem, 0));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(du, ddu, (size_t)N * (n + 1) * 8, hipMemcpyDeviceToHost));
     return 0;

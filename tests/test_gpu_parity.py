@@ -791,7 +791,8 @@ def test_quad_engine_h2o2(pkg, orc, gpu, monkeypatch):
 
 def test_launch_info_follows_the_engine(pkg, orc, gpu, monkeypatch):
     """br_mech_launch_info (the bench line's roofline.launch) describes the engine br_integrate
-    launches: the quad engine's workgroups hold 4 reactors per wave, the wavefront engine's one."""
+    launches: the quad engine's workgroups hold 4 reactors per wave, the wavefront engine's one, the lane
+    engine's one wave of 64 reactors (within its 64 KB of LDS), the pair engine's 2 reactors per wave."""
     pm, _ = _mechs(pkg, orc, "h2o2")
     monkeypatch.setenv("BRHIP_ENGINE", "quad")
     q = pkg.Engine(pm).launch_info
@@ -801,6 +802,19 @@ def test_launch_info_follows_the_engine(pkg, orc, gpu, monkeypatch):
     assert 1 <= q["waves_per_cu"] <= 32 and 1 <= w["waves_per_cu"] <= 32, (q, w)
     assert 0 < q["lds_bytes_per_workgroup"] <= 160 * 1024 and 0 < w["lds_bytes_per_workgroup"] <= 160 * 1024
     assert q != w
+    monkeypatch.setenv("BRHIP_ENGINE", "lane")
+    le = pkg.Engine(pm)
+    assert le.engine == "lane"
+    ln = le.launch_info
+    assert ln["reactors_per_workgroup"] == 64 and ln["waves_per_cu"] >= 1, ln
+    assert 0 < ln["lds_bytes_per_workgroup"] <= 64 * 1024, ln
+    sm, _ = _mechs(pkg, orc, "surf")
+    monkeypatch.setenv("BRHIP_ENGINE", "pair")
+    pe = pkg.Engine(sm)
+    assert pe.engine == "pair"
+    p = pe.launch_info
+    assert p["reactors_per_workgroup"] % 2 == 0 and p["reactors_per_workgroup"] >= 2, p
+    assert 1 <= p["waves_per_cu"] <= 32 and 0 < p["lds_bytes_per_workgroup"] <= 160 * 1024, p
 
 
 def test_quad_engine_dq_jacobian(pkg, orc, gpu, monkeypatch):
